@@ -21,6 +21,13 @@ per rank instead ("scaling": "weak"; DESIGN.md §6 has both).
   python bench.py --workload vilt_train   ViLT classification training step (forward, backward, AdamW)
 
 Rank 0 prints one JSON line (see README/DESIGN for the field definitions).
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what takes
+runs of its own: the CPU baseline (the oracle on the host cores; --no-cpu-baseline drops it
+again) and, where the step is replayed as a HIP graph, the eager steps that time the GEMM /
+fused-block rooflines.  --dump-outputs DIR writes what the last timed step returned (loss,
+logits, a seeded sample of the updated parameters, ...) as DIR/<name>.npy; the inputs and the
+initial weights are seeded, so two builds run with the same arguments compare output for output.
 """
 import argparse
 import json
@@ -32,9 +39,30 @@ import time
 REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path[:0] = [os.path.join(REPO, "multi-modal-uncertainty_amd"), REPO]
 
+
+def _miopen_user_db():
+    """A working copy (under the ignored build/ directory) of the find-db shipped in
+    multi-modal-uncertainty_amd/miopen_db: MIOpen rewrites its user db whenever it searches a
+    shape that is not in it yet, and that must not touch the committed files."""
+    import shutil
+    src = os.path.join(REPO, "multi-modal-uncertainty_amd", "miopen_db")
+    dst = os.path.join(REPO, "multi-modal-uncertainty_amd", "build", "miopen_db")
+    try:
+        os.makedirs(dst, exist_ok=True)
+        for name in os.listdir(src):
+            have = os.path.join(dst, name)
+            if name.endswith(".txt") and not (os.path.exists(have) and
+                                              os.path.getmtime(have) >= os.path.getmtime(os.path.join(src, name))):
+                tmp = os.path.join(dst, f".{name}.{os.getpid()}")
+                shutil.copyfile(os.path.join(src, name), tmp)
+                os.replace(tmp, os.path.join(dst, name))   # ranks starting together: whole files only
+    except OSError:
+        return src
+    return dst
+
+
 # MIOpen reads its user db path when its first handle is created (first conv)
-os.environ.setdefault("MIOPEN_USER_DB_PATH", os.path.join(os.path.dirname(os.path.abspath(__file__)),
-                                                          "multi-modal-uncertainty_amd", "miopen_db"))
+os.environ.setdefault("MIOPEN_USER_DB_PATH", _miopen_user_db())
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
@@ -59,7 +87,13 @@ def parse(argv=None):
     ap.add_argument("--per-rank-batch", type=int, default=None,
                     help="samples per rank per step instead (weak scaling)")
     ap.add_argument("--text-len", type=int, default=508, help="word-pieces per sample (L = 5 + this)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what needs runs of its own: the CPU baseline and, under --graph, the "
+                         "rooflines' eager steps before the capture (a plain run leaves those fields out / null)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned as DIR/<name>.npy (float32; "
+                         "a seeded sample of anything too large, at most 64 MB in all)")
     ap.add_argument("--sync-bn", action="store_true",
                     help="mmbt, N > 1: the trunk's BatchNorms normalise over the whole global batch (cross-rank sums)")
     ap.add_argument("--main-priority", default="normal", choices=["normal", "high"],
@@ -91,6 +125,54 @@ def parse(argv=None):
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="CPU-baseline threads (0: os.cpu_count(), SURVEY §8(d)'s torch.set_num_threads(os.cpu_count()))")
     return ap.parse_args(argv)
+
+
+DUMP_BUDGET_BYTES = 60 << 20   # of the 64 MB a dump may take (the .npy headers are small)
+PARAM_SAMPLE = 4096            # elements kept of every parameter tensor
+
+
+def _sample(t, n, seed):
+    """``t`` flattened; when it has more than ``n`` elements, the ones at ``n`` seeded random
+    positions (the same positions for the same shape and seed, whatever the build)."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() <= n:
+        return flat
+    idx = torch.randint(0, flat.numel(), (n,), generator=torch.Generator().manual_seed(seed))
+    return flat[idx.to(flat.device)]
+
+
+def params_sample(params):
+    """A fixed sample of the parameters a train step updated: PARAM_SAMPLE seeded positions of each."""
+    return torch.cat([_sample(p, PARAM_SAMPLE, 7000 + i).float() for i, p in enumerate(params)])
+
+
+def _tensors(obj, prefix, out):
+    """Flatten what a step returned (tensor, tuple / list / dict of them, a transformers
+    ModelOutput) into name -> tensor."""
+    if torch.is_tensor(obj):
+        out[prefix] = obj
+    elif isinstance(obj, dict):
+        for k, v in obj.items():
+            _tensors(v, f"{prefix}_{k}", out)
+    elif isinstance(obj, (tuple, list)):
+        for i, v in enumerate(obj):
+            _tensors(v, f"{prefix}_{i}", out)
+    return out
+
+
+def dump_outputs(path, arrays):
+    """Write name -> tensor as path/<name>.npy in float32 (float64 stays); every array gets an equal
+    share of DUMP_BUDGET_BYTES and is a seeded sample of itself where it is larger."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(arrays), 1)
+    for i, (name, t) in enumerate(sorted(arrays.items())):
+        t = torch.as_tensor(t).detach()
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        n = share // (8 if dt == torch.float64 else 4)
+        if t.numel() > n:
+            t = _sample(t, n, 9000 + i)
+        np.save(os.path.join(path, name + ".npy"), t.to(dt).cpu().numpy())
 
 
 def rank_launch_cmd(n, argv, port):
@@ -280,7 +362,8 @@ def bench_flava(args, world, rank, dev):
 
     def step():
         opt.zero_grad()
-        loss = model.compute_loss(model((img, txt)), y)
+        logits = model((img, txt))
+        loss = model.compute_loss(logits, y)
         loss.backward()
         if world > 1:
             grads = [p.grad for p in params]
@@ -291,7 +374,7 @@ def bench_flava(args, world, rank, dev):
                 gr.copy_(f)
         opt.step()
         sched.step()
-        return loss
+        return loss, logits
 
     for _ in range(args.warmup):
         step()
@@ -304,13 +387,16 @@ def bench_flava(args, world, rank, dev):
         dist.barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, logits = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
     block_ms, block_n = encoder.block_timing_read()
     encoder.block_timing(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(_tensors(logits, "logits", {}), loss=loss,
+                                             params_sample=params_sample(params)))
     if world > 1:
         t = torch.tensor([dt], device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -335,7 +421,7 @@ def bench_flava(args, world, rank, dev):
             "share_of_step": round(block_ms / args.steps / ms_step, 3) if ms_step else None},
         "final_loss": round(float(loss.item()), 4),
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = flava_cpu_baseline(args, L_img, L_txt)
     return out
 
@@ -406,6 +492,7 @@ def bench_uncertainty(args, world, rank, dev):
             lo = ens.logits(*x, mc_samples=T_mc)                         # [K, T, B, C]
             flat = lo.permute(2, 0, 1, 3).reshape(B, Km * T_mc, lo.shape[-1])
             meter.update(flat, y)
+        return lo
 
     for _ in range(args.warmup):
         step()
@@ -416,7 +503,7 @@ def bench_uncertainty(args, world, rank, dev):
     meter = UncertaintyMeter(15)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        lo = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -428,6 +515,9 @@ def bench_uncertainty(args, world, rank, dev):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
     res = meter.result()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"logits": lo, "metrics": torch.tensor(
+            [res["nll"], res["ece"], res["acc"]], dtype=torch.float64)})
     H = 768
     layer_fwd = L * (24 * H * H + 4 * L * H)             # per sequence per layer, forward
     seqs = Km * T_mc * B
@@ -452,7 +542,7 @@ def bench_uncertainty(args, world, rank, dev):
         "model_tflops_achieved": round(flop_step * world / (ms_step * 1e-3) / 1e12, 1),
         "nll": round(res["nll"], 5), "ece": round(res["ece"], 5), "acc": round(res["acc"], 5),
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = uncertainty_cpu_baseline(args, T)
     return out
 
@@ -499,10 +589,13 @@ def bench_vilt_train(args, world, rank, dev):
                  pixel_values=torch.randn(B, 1, 3, cfg.image_size, cfg.image_size, generator=g).to(dev),
                  labels=torch.randint(0, 2, (B,), generator=g).to(dev))
 
+    last = [None]
+
     def step():
         opt.zero_grad()
         out = hip(**batch)
         out.loss.backward()
+        last[0] = out
         if world > 1:
             grads = [p.grad for p in params]
             flat = torch._utils._flatten_dense_tensors(grads)
@@ -527,6 +620,9 @@ def bench_vilt_train(args, world, rank, dev):
     dt = time.perf_counter() - t0
     gemm_ms, gemm_n, gemm_flop = K.timing_read()
     K.timing_enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": last[0].loss, "logits": last[0].logits,
+                                         "params_sample": params_sample(params)})
     if world > 1:
         t = torch.tensor([dt], device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -547,7 +643,7 @@ def bench_vilt_train(args, world, rank, dev):
                      "gemm_launches_timed": gemm_n, "gemm_ms_per_step": round(gemm_ms / args.steps, 3)},
         "model_tflops_achieved": round(flop_sample * B * world / (ms_step * 1e-3) / 1e12, 1),
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         ref = ViltForImagesAndTextClassification(cfg).train()
         ropt = torch.optim.AdamW(ref.parameters(), lr=1e-4)
         cb = {k: v[:2].cpu() for k, v in batch.items()}
@@ -620,13 +716,15 @@ def bench_encoders(args, world, rank, dev):
     K.timing_enable(True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        run()
+        res = run()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
     gemm_ms, gemm_n, gemm_flop = K.timing_read()
     K.timing_enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, _tensors(res.to_tuple() if hasattr(res, "to_tuple") else res, "out", {}))
     if world > 1:
         t = torch.tensor([dt], device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -651,13 +749,21 @@ def bench_encoders(args, world, rank, dev):
                      "gemm_launches_timed": gemm_n, "gemm_ms_per_step": round(gemm_ms / args.steps, 3)},
         "model_tflops_achieved": round(flop_sample * B * world / (ms_step * 1e-3) / 1e12, 1),
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = _encoder_cpu_baseline(args, cpu_run, 2, what)
     return out
 
 
 def main():
     args = parse()
+    # Which solvers MIOpen's find may try (read at the first conv; set here, not at import, so
+    # that only benchmark runs are affected).  Every new process searches each conv shape again
+    # whatever the find-db holds (the records come back rewritten with new timings), and the
+    # search compiles and times the naive direct convolutions too: 20-300 ms a run at batch 256
+    # against 0.06-0.3 ms for the implicit-GEMM solvers that always win (miopen_db/*.ufdb.txt),
+    # ~30 s before the first step ends.  Without them the find picks the same solvers.
+    for d in ("FWD", "BWD", "WRW"):
+        os.environ.setdefault("MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_" + d, "0")
     world, launch = resolve_world(args)
     if launch:
         # no launcher around us: start the N ranks (one per GPU) as a child torch.distributed.run
@@ -762,12 +868,13 @@ def main():
 
     def step():
         opt.zero_grad()
-        loss = model.compute_loss(model(*x), y)
+        logits = model(*x)
+        loss = model.compute_loss(logits, y)
         loss.backward()
         if bucketer is not None:
             bucketer.finish()
         opt.step()
-        return loss
+        return loss, logits
 
     graph = args.graph == "on" or (args.graph == "auto" and world == 1 and B <= 64)
     if graph and world > 1:
@@ -775,21 +882,23 @@ def main():
         # one-GPU boxes this was developed on cannot exercise)
         raise SystemExit("--graph on: single-process runs only (N = 1)")
     run = step
+    rooflines = args.full or not graph   # eager steps time their own launches; a replay needs steps apart
     if graph:
-        # the rooflines' per-launch timings from 2 eager steps (the same kernels the graph replays)
-        step()
-        K.timing_enable(True)
-        encoder.block_timing(True)
-        for _ in range(2):
+        if rooflines:
+            # the rooflines' per-launch timings from 2 eager steps (the same kernels the graph replays)
             step()
-        torch.cuda.synchronize()
-        gemm_ms, gemm_n, gemm_flops = K.timing_read()
-        alg_bytes, _ = K.timing_alg_bytes()
-        K.timing_enable(False)
-        block_ms, block_n = encoder.block_timing_read()
-        encoder.block_timing(False)
-        timed_steps = 2
-        torch.cuda.empty_cache()
+            K.timing_enable(True)
+            encoder.block_timing(True)
+            for _ in range(2):
+                step()
+            torch.cuda.synchronize()
+            gemm_ms, gemm_n, gemm_flops = K.timing_read()
+            alg_bytes, _ = K.timing_alg_bytes()
+            K.timing_enable(False)
+            block_ms, block_n = encoder.block_timing_read()
+            encoder.block_timing(False)
+            timed_steps = 2
+            torch.cuda.empty_cache()
         from src.graphs import StepGraph
         sg = StepGraph(step, dev, warmup=2)
         run = sg.replay
@@ -807,7 +916,7 @@ def main():
         dist.barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = run()
+        loss, logits = run()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -822,12 +931,18 @@ def main():
         t = torch.tensor([dt], device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": loss, "logits": logits,
+                                         "params_sample": params_sample(model.parameters())})
     ms_step = 1000.0 * dt / args.steps
     traffic = gemm_traffic(B)
     value = args.global_batch * args.steps / dt
     H = 768
     layer_fwd = L * (24 * H * H + 4 * L * H)
     model_flop = 3 * (12 * layer_fwd + RESNET152_FWD_FLOP)
+    if not rooflines:
+        gemm_ms = gemm_n = gemm_flops = alg_bytes = block_ms = block_n = 0
+        timed_steps = 1
     achieved = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
     block_tf = 3 * layer_fwd * B * (block_n / 2) / (block_ms * 1e-3) / 1e12 if block_ms > 0 else 0.0
     out = {
@@ -864,8 +979,11 @@ def main():
         "final_loss": round(float(loss.item()), 4),
         "hbm_peak_gb": round(torch.cuda.max_memory_allocated(dev) / 1e9, 1),
     }
+    if not rooflines:
+        # a graph replay has no per-launch events and a plain run no eager steps for them
+        out["roofline"] = out["fused_block_roofline"] = None
     out["world_size_reported"] = dist.get_world_size() if dist.is_initialized() else 1
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, T)
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -131,19 +131,65 @@ def test_gin_parser_and_mapping():
         gin.parse_bindings("train.lr = [1,\n")
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/configs"), reason="reference configs not present")
-def test_gin_parses_reference_configs():
-    """Every .gin file the reference ships parses; train.* bindings land on train flags."""
-    import glob
+GIN_TRAINING = """# Model
+Net.pretrained=False
+Net.num_views=2
+Net.weights_path='/data/runs/two views/model_best_val.pt'
+Net.device='cuda:0'
+
+# Train configuration
+train.batch_size=8
+train.lr=0.1
+train.wd=0.0
+train.momentum=0
+train.callbacks=['EarlyStop', 'PlateauLR', 'Rebalance']
+PlateauLR.metric='loss'
+EarlyStop.patience=5
+Rebalance.epsilon=0.01
+Rebalance.branch_names = ['view_0', 'view_1']
+Progress.other_metrics=[]
+
+
+# Training loop
+training_loop.n_epochs=300
+training_loop.use_gpu=True
+training_loop.device_numbers=[0]
+training_loop.checkpoint_monitor='val_acc'
+
+# Dataset
+get_data.make_npy_files=False
+get_data.specific_views=[0, 6]
+"""
+
+GIN_EVAL = """# Train configuration
+eval_.target_data_split='test'
+eval_.batch_size=8
+evalution_loop.use_gpu=True
+evalution_loop.save_with_structure=False
+"""
+
+
+def test_gin_parses_config_files(tmp_path):
+    """Config files in the layout gin projects keep (section comments, blank lines, scoped bindings
+    with and without spaces round '=', quoted paths, booleans, empty and int lists) parse from
+    disk; train.* bindings land on train flags with the flag's type."""
     import types
-    files = sorted(glob.glob("/root/reference/configs/*.gin"))
-    assert len(files) == 5
-    for f in files:
-        b = gin.parse_bindings(open(f).read())
-        assert b, f
-    args = types.SimpleNamespace(batch_size=32, lr=0.5, wd=0.1, momentum=0.9)
-    gin.load(args, [os.path.join("/root/reference/configs", "training.gin")])
-    assert (args.batch_size, args.lr, args.wd, args.momentum) == (8, 0.1, 0.0, 0)
+    files = {"training.gin": GIN_TRAINING, "eval.gin": GIN_EVAL}
+    for name, text in files.items():
+        (tmp_path / name).write_text(text)
+        b = gin.parse_bindings((tmp_path / name).read_text())
+        assert len(b) == sum(1 for ln in text.splitlines() if "=" in ln), name
+    b = gin.parse_bindings(GIN_TRAINING)
+    assert b["Net.pretrained"] is False and b["Net.weights_path"] == "/data/runs/two views/model_best_val.pt"
+    assert b["Rebalance.branch_names"] == ["view_0", "view_1"] and b["Progress.other_metrics"] == []
+    assert b["get_data.specific_views"] == [0, 6] and b["training_loop.device_numbers"] == [0]
+    args = types.SimpleNamespace(batch_size=32, lr=0.5, wd=0.1, momentum=0.9, n_epochs=10)
+    unused = gin.load(args, [str(tmp_path / "training.gin")])
+    assert (args.batch_size, args.lr, args.wd, args.momentum, args.n_epochs) == (8, 0.1, 0.0, 0, 300)
+    assert isinstance(args.momentum, float) and "train.callbacks" in unused and "Net.device" in unused
+    args = types.SimpleNamespace(batch_size=32, target_data_split="val")
+    gin.load(args, [str(tmp_path / "training.gin"), str(tmp_path / "eval.gin")])
+    assert (args.batch_size, args.target_data_split) == (8, "test")
 
 
 @pytest.mark.parametrize("mt", ["MultiHead", "single-model-weight-sharing"])
