@@ -406,7 +406,9 @@ int mmu_attention_bwd(const void* QKV, int64_t ld_qkv, const float* keymask, con
   if ((uint32_t)(drop_p * 65536.0f + 0.5f) != 0 && !dropmask)
     return fail("mmu_attention_bwd: dropout needs the forward's dropmask");
   if (attn_common(ld_qkv, batch, L, heads, drop_p)) return 1;
-  if (ld_dqkv < 3 * heads * 64 || ld_do % 8 || ld_o % 8 || ld_dqkv % 4) return fail("mmu_attention_bwd: bad ld");
+  // (ld_o / ld_do below the row width: rows would overlap and the last one be read past the buffer)
+  if (ld_dqkv < 3 * heads * 64 || ld_do < heads * 64 || ld_o < heads * 64 || ld_do % 8 || ld_o % 8 || ld_dqkv % 4)
+    return fail("mmu_attention_bwd: bad ld");
   if (batch * heads > 65535) return fail("mmu_attention_bwd: batch*heads > 65535");
   AttnParams p{};
   p.qkv = (const bf16*)QKV; p.ld_qkv = ld_qkv; p.keymask = keymask; p.o = (const bf16*)O; p.ld_o = ld_o;
