@@ -294,42 +294,109 @@ def attention_bwd(qkv, keymask, O, dO, lse, delta, dqkv, batch, L, heads=12, dro
            _ptr(dropmask) if dropmask is not None else None, _ptr(dbias_parts), _stream(qkv))
 
 
-def layernorm_fwd(X, w, b, Y, mean, rstd, eps=1e-12, group_rows=0, param_stride=0):
-    _dev_check(X, w, b, Y, mean, rstd)
+LN_ROWS_PER_PART = 64
+
+
+def ln_parts(rows):
+    return (rows + LN_ROWS_PER_PART - 1) // LN_ROWS_PER_PART
+
+
+def _ln_rows(who, X, x_dtype, same=(), vecs=(), parts=()):
+    """Host-side argument checks of the LayerNorm wrappers (shapes and dtypes only: no device
+    read, no sync).  X: the [rows, H] input of dtype x_dtype; same: (name, tensor or None) bf16
+    tensors of X's shape; vecs: (name, tensor or None) f32 per-row vectors of >= rows elements;
+    parts: (name, tensor or None) f32 partial column sums of >= ln_parts(rows) * H elements.
+    -> rows, H"""
+    if X.dim() != 2 or not X.is_contiguous():
+        raise N.NativeError(f"{who}: X must be a contiguous 2-D [rows, H] tensor, got {tuple(X.shape)}")
+    _want(X, x_dtype, f"{who} X")
     rows, H = X.shape
+    for name, t in same:
+        if t is None:
+            continue
+        _want(t, torch.bfloat16, f"{who} {name}")
+        if t.shape != X.shape or not t.is_contiguous():
+            raise N.NativeError(f"{who}: {name} must be contiguous [{rows}, {H}] like X, got {tuple(t.shape)}")
+    for name, t in vecs:
+        if t is None:
+            continue
+        _want(t, torch.float32, f"{who} {name}")
+        if t.numel() < rows or not t.is_contiguous():
+            raise N.NativeError(f"{who}: {name} must hold >= {rows} contiguous elements, got {t.numel()}")
+    need = ln_parts(rows) * H
+    for name, t in parts:
+        if t is None:
+            continue
+        _want(t, torch.float32, f"{who} {name}")
+        if t.numel() < need or not t.is_contiguous():
+            raise N.NativeError(f"{who}: {name} must hold >= ln_parts(rows) x H = {need} contiguous elements, "
+                                f"got {t.numel()}")
+    return rows, H
+
+
+def _ln_params(who, rows, H, group_rows, param_stride, **params):
+    """f32 contiguous affine parameters of (groups - 1) * param_stride + H elements, rows a
+    multiple of group_rows (0: one group)"""
+    group_rows, param_stride = int(group_rows), int(param_stride)
+    groups = 1
+    if group_rows > 0:
+        if rows % group_rows:
+            raise N.NativeError(f"{who}: rows = {rows} is no multiple of group_rows = {group_rows}")
+        groups = rows // group_rows
+    if param_stride < 0:
+        raise N.NativeError(f"{who}: bad param_stride {param_stride}")
+    need = (groups - 1) * param_stride + H
+    for name, t in params.items():
+        _want(t, torch.float32, f"{who} {name}")
+        if t.numel() < need or not t.is_contiguous():
+            raise N.NativeError(f"{who}: {name} must hold (groups - 1) * param_stride + H = {need} contiguous "
+                                f"elements, got {t.numel()}")
+
+
+def layernorm_fwd(X, w, b, Y, mean, rstd, eps=1e-12, group_rows=0, param_stride=0):
+    rows, H = _ln_rows("layernorm_fwd", X, torch.bfloat16, same=(("Y", Y),), vecs=(("mean", mean), ("rstd", rstd)))
+    _ln_params("layernorm_fwd", rows, H, group_rows, param_stride, w=w, b=b)
+    _dev_check(X, w, b, Y, mean, rstd)
     N.call("mmu_layernorm_fwd", _ptr(X), _ptr(w), _ptr(b), _ptr(Y), _ptr(mean), _ptr(rstd), rows, H, float(eps),
            int(group_rows), int(param_stride), _stream(X))
 
 
 def layernorm_fwd_f32(X, w, b, Y, Y32=None, mean=None, rstd=None, eps=1e-12, group_rows=0, param_stride=0):
     """LN of the f32 hidden stream: X f32 -> Y bf16 (GEMM operand) [+ Y32 f32 (next residual)]."""
-    _dev_check(X, w, b, Y)
-    _want(X, torch.float32, "layernorm_fwd_f32 X")
-    _want(Y, torch.bfloat16, "layernorm_fwd_f32 Y")
+    rows, H = _ln_rows("layernorm_fwd_f32", X, torch.float32, same=(("Y", Y),),
+                       vecs=(("mean", mean), ("rstd", rstd)))
     if Y32 is not None:
         _want(Y32, torch.float32, "layernorm_fwd_f32 Y32")
-    rows, H = X.shape
+        if Y32.shape != X.shape or not Y32.is_contiguous():
+            raise N.NativeError(f"layernorm_fwd_f32: Y32 must be contiguous [{rows}, {H}] like X, got "
+                                f"{tuple(Y32.shape)}")
+    _ln_params("layernorm_fwd_f32", rows, H, group_rows, param_stride, w=w, b=b)
+    _dev_check(X, w, b, Y, Y32, mean, rstd)
     N.call("mmu_layernorm_fwd_f32", _ptr(X), _ptr(w), _ptr(b), _ptr(Y), _ptr(Y32), _ptr(mean), _ptr(rstd), rows, H,
            float(eps), int(group_rows), int(param_stride), _stream(X))
-
-
-LN_ROWS_PER_PART = 64
 
 
 def layernorm_bwd(dY, X, mean, rstd, w, dX, dXdrop=None, drop_p=0.0, seed=0, part_dw=None, part_db=None,
                   part_dbias=None):
     """X: the forward's LN input, bf16 or f32 (the f32 hidden stream: mmu_layernorm_bwd_f32)."""
-    _dev_check(dY, X, mean, rstd, w, dX)
-    rows, H = X.shape
-    N.call("mmu_layernorm_bwd_f32" if X.dtype == torch.float32 else "mmu_layernorm_bwd", _ptr(dY), _ptr(X), _ptr(mean), _ptr(rstd), _ptr(w), _ptr(dX), _ptr(dXdrop),
-           float(drop_p), int(seed), _ptr(part_dw), _ptr(part_db), _ptr(part_dbias), rows, H, LN_ROWS_PER_PART,
-           _stream(X))
+    x32 = X.dtype == torch.float32
+    rows, H = _ln_rows("layernorm_bwd", X, torch.float32 if x32 else torch.bfloat16,
+                       same=(("dY", dY), ("dX", dX), ("dXdrop", dXdrop)), vecs=(("mean", mean), ("rstd", rstd)),
+                       parts=(("part_dw", part_dw), ("part_db", part_db), ("part_dbias", part_dbias)))
+    _ln_params("layernorm_bwd", rows, H, 0, 0, w=w)
+    _dev_check(dY, X, mean, rstd, w, dX, dXdrop, part_dw, part_db, part_dbias)
+    N.call("mmu_layernorm_bwd_f32" if x32 else "mmu_layernorm_bwd", _ptr(dY), _ptr(X), _ptr(mean), _ptr(rstd),
+           _ptr(w), _ptr(dX), _ptr(dXdrop), float(drop_p), int(seed), _ptr(part_dw), _ptr(part_db), _ptr(part_dbias),
+           rows, H, LN_ROWS_PER_PART, _stream(X))
 
 
 def layernorm_bwd_res(dY, X, mean, rstd, w, dRes, dX, part_dw=None, part_db=None, part_dbias=None):
     """Pre-LN backward: dX = LN'(dY) + dRes (part_dbias = column sums of that dX)."""
-    _dev_check(dY, X, mean, rstd, w, dRes, dX)
-    rows, H = X.shape
+    rows, H = _ln_rows("layernorm_bwd_res", X, torch.bfloat16, same=(("dY", dY), ("dRes", dRes), ("dX", dX)),
+                       vecs=(("mean", mean), ("rstd", rstd)),
+                       parts=(("part_dw", part_dw), ("part_db", part_db), ("part_dbias", part_dbias)))
+    _ln_params("layernorm_bwd_res", rows, H, 0, 0, w=w)
+    _dev_check(dY, X, mean, rstd, w, dRes, dX, part_dw, part_db, part_dbias)
     N.call("mmu_layernorm_bwd_res", _ptr(dY), _ptr(X), _ptr(mean), _ptr(rstd), _ptr(w), _ptr(dRes), _ptr(dX),
            _ptr(part_dw), _ptr(part_db), _ptr(part_dbias), rows, H, LN_ROWS_PER_PART, _stream(X))
 
@@ -354,17 +421,67 @@ def seqattn_bwd(qkv, O, dO, lse2, delta, dqkv, S, N_, heads):
            _ptr(delta), _ptr(dqkv), dqkv.stride(0), S, N_, heads, D, _stream(qkv))
 
 
-def ln_parts(rows):
-    return (rows + LN_ROWS_PER_PART - 1) // LN_ROWS_PER_PART
+def _embed_common(who, ids, seg, proj, word, pos, typ, ln_w, cls_id, sep_id, B, T, n_img):
+    """Host-side argument checks shared by embed_fwd / embed_bwd (shapes and dtypes only; the
+    values of ids / seg / idx are not read)"""
+    B, T, n_img = int(B), int(T), int(n_img)
+    for name, t in (("ids", ids), ("seg", seg)):
+        _want(t, torch.int64, f"{who} {name}")
+        if tuple(t.shape) != (B, T) or not t.is_contiguous():
+            raise N.NativeError(f"{who}: {name} must be contiguous int64 [B, T] = [{B}, {T}], got {tuple(t.shape)}")
+    _want(proj, torch.float32, f"{who} proj")
+    if tuple(proj.shape) != (B, n_img, 768) or not proj.is_contiguous():
+        raise N.NativeError(f"{who}: proj must be contiguous f32 [B, n_img, 768] = [{B}, {n_img}, 768], got "
+                            f"{tuple(proj.shape)}")
+    for name, t in (("word", word), ("pos", pos), ("typ", typ)):
+        _want(t, torch.float32, f"{who} {name}")
+        if t.dim() != 2 or t.shape[1] != 768 or not t.is_contiguous():
+            raise N.NativeError(f"{who}: {name} must be a contiguous f32 [n, 768] table, got {tuple(t.shape)}")
+    _want(ln_w, torch.float32, f"{who} ln_w")
+    if ln_w.numel() != 768 or not ln_w.is_contiguous():
+        raise N.NativeError(f"{who}: ln_w must hold 768 contiguous elements, got {ln_w.numel()}")
+    if max(n_img + 2, T) > pos.shape[0]:
+        raise N.NativeError(f"{who}: max(n_img + 2, T) = {max(n_img + 2, T)} exceeds the {pos.shape[0]} position rows")
+    if not (0 <= int(cls_id) < word.shape[0] and 0 <= int(sep_id) < word.shape[0]):
+        raise N.NativeError(f"{who}: cls_id / sep_id = {cls_id} / {sep_id} outside the {word.shape[0]} word rows")
+    if typ.shape[0] < 2:
+        raise N.NativeError(f"{who}: typ must hold >= 2 token-type rows, got {typ.shape[0]}")
 
 
 def embed_fwd(ids, seg, txt_mask, proj, word, pos, typ, ln_w, ln_b, eps, cls_id, sep_id, idx, V, B, T, n_img, Lout,
               X, keymask, mean=None, rstd=None, drop_txt=0.0, drop_img=0.0, seed=0, X32=None):
     """X32 (optional, f32 like X): the same rows in f32, the encoder's f32 hidden stream."""
-    _dev_check(proj, word, pos, typ, ln_w, ln_b, X, keymask)
-    if X32 is not None:
-        _want(X32, torch.float32, "embed_fwd X32")
-        _dev_check(X32)
+    who = "embed_fwd"
+    _embed_common(who, ids, seg, proj, word, pos, typ, ln_w, cls_id, sep_id, B, T, n_img)
+    rows = int(V) * int(B) * int(Lout)
+    if txt_mask is not None:
+        _want(txt_mask, torch.int64, f"{who} txt_mask")
+        if tuple(txt_mask.shape) != (B, T) or not txt_mask.is_contiguous():
+            raise N.NativeError(f"{who}: txt_mask must be contiguous int64 [B, T] = [{B}, {T}], got "
+                                f"{tuple(txt_mask.shape)}")
+    _want(ln_b, torch.float32, f"{who} ln_b")
+    if ln_b.numel() != 768 or not ln_b.is_contiguous():
+        raise N.NativeError(f"{who}: ln_b must hold 768 contiguous elements, got {ln_b.numel()}")
+    if idx is not None:
+        _want(idx, torch.int64, f"{who} idx")
+        if tuple(idx.shape) != (V, Lout) or not idx.is_contiguous():
+            raise N.NativeError(f"{who}: idx must be contiguous int64 [V, Lout] = [{V}, {Lout}], got "
+                                f"{tuple(idx.shape)}")
+    for name, t, dt in (("X", X, torch.bfloat16), ("X32", X32, torch.float32)):
+        if t is None:
+            continue
+        _want(t, dt, f"{who} {name}")
+        if tuple(t.shape) != (rows, 768) or not t.is_contiguous():
+            raise N.NativeError(f"{who}: {name} must be contiguous [V * B * Lout, 768] = [{rows}, 768], got "
+                                f"{tuple(t.shape)}")
+    for name, t in (("keymask", keymask), ("mean", mean), ("rstd", rstd)):
+        if t is None:
+            continue
+        _want(t, torch.float32, f"{who} {name}")
+        if t.numel() < rows or not t.is_contiguous():
+            raise N.NativeError(f"{who}: {name} must hold >= V * B * Lout = {rows} contiguous elements, got "
+                                f"{t.numel()}")
+    _dev_check(ids, seg, txt_mask, idx, proj, word, pos, typ, ln_w, ln_b, X, X32, keymask, mean, rstd)
     N.call("mmu_embed_fwd", _ptr(ids), _ptr(seg), _ptr(txt_mask), _ptr(proj), _ptr(word), _ptr(pos), _ptr(typ),
            _ptr(ln_w), _ptr(ln_b), float(eps), int(cls_id), int(sep_id), _ptr(idx), V, B, T, n_img, Lout, 768,
            float(drop_txt), float(drop_img), int(seed), _ptr(X), _ptr(X32), _ptr(keymask), _ptr(mean), _ptr(rstd),
@@ -373,7 +490,24 @@ def embed_fwd(ids, seg, txt_mask, proj, word, pos, typ, ln_w, ln_b, eps, cls_id,
 
 def embed_bwd(dX, ids, seg, proj, word, pos, typ, ln_w, mean, rstd, cls_id, sep_id, B, T, n_img, d_word, d_pos,
               d_type, d_ln_w, d_ln_b, d_proj, drop_txt=0.0, drop_img=0.0, seed=0):
-    _dev_check(dX, proj, word, d_word, d_proj)
+    who = "embed_bwd"
+    _embed_common(who, ids, seg, proj, word, pos, typ, ln_w, cls_id, sep_id, B, T, n_img)
+    rows = int(B) * (int(n_img) + 2 + int(T))
+    _want(dX, torch.bfloat16, f"{who} dX")
+    if tuple(dX.shape) != (rows, 768) or not dX.is_contiguous():
+        raise N.NativeError(f"{who}: dX must be contiguous bf16 [B * (n_img + 2 + T), 768] = [{rows}, 768], got "
+                            f"{tuple(dX.shape)}")
+    for name, t in (("mean", mean), ("rstd", rstd)):
+        _want(t, torch.float32, f"{who} {name}")
+        if t.numel() < rows or not t.is_contiguous():
+            raise N.NativeError(f"{who}: {name} must hold >= {rows} contiguous elements, got {t.numel()}")
+    for name, t, like in (("d_word", d_word, word), ("d_pos", d_pos, pos), ("d_type", d_type, typ),
+                          ("d_ln_w", d_ln_w, ln_w), ("d_ln_b", d_ln_b, ln_w), ("d_proj", d_proj, proj)):
+        _want(t, torch.float32, f"{who} {name}")
+        if t.shape != like.shape or not t.is_contiguous():
+            raise N.NativeError(f"{who}: {name} must be contiguous f32 {tuple(like.shape)} like its parameter, got "
+                                f"{tuple(t.shape)}")
+    _dev_check(dX, ids, seg, proj, word, pos, typ, ln_w, mean, rstd, d_word, d_pos, d_type, d_ln_w, d_ln_b, d_proj)
     ws = torch.empty(N.load().mmu_embed_bwd_ws_floats(B, T, n_img), dtype=torch.float32, device=dX.device)
     N.call("mmu_embed_bwd", _ptr(dX), _ptr(ids), _ptr(seg), _ptr(proj), _ptr(word), _ptr(pos), _ptr(typ),
            _ptr(ln_w), _ptr(mean), _ptr(rstd), int(cls_id), int(sep_id), B, T, n_img, 768, float(drop_txt),

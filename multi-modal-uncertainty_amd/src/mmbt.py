@@ -436,6 +436,8 @@ class MultimodalBertEncoder(nn.Module):
                                              txt_mask, drop_txt, drop_img, seed)
             return (X, X32), km, self.n_img + 2 + T
         L = self.n_img + 2 + T if idx is None else Lout
+        if idx is not None:
+            idx = idx.reshape(V, L)  # (the variant forwards pass one 1-D index set)
         X = torch.empty(V * B * L, 768, dtype=torch.bfloat16, device=dev)
         X32 = torch.empty(V * B * L, 768, dtype=torch.float32, device=dev)
         km = torch.empty(V * B, L, dtype=torch.float32, device=dev)

@@ -1,0 +1,91 @@
+"""Guarded device buffers for the kernel edge sweeps (test_attention_edges_gpu.py,
+test_layernorm_edges_gpu.py, test_embed_edges_gpu.py): every tensor a kernel sees is a view of a
+larger allocation.  Input guards hold NaN, so a read through them poisons the result; outputs are
+pre-filled with a canary, and afterwards everything outside the view must be bit-identical to it.
+  out_buf / check_written: NaN-filled contiguous outputs and their check after a launch;
+  probe_keep: the keep bits of the GEMM's BIAS_DROP_RES epilogue, read from the epilogue itself.
+"""
+import torch
+
+NAN = float("nan")
+bf16 = torch.bfloat16
+
+G = 2          # guard rows on each side of a 2-D buffer
+G1 = 8         # guard elements on each side of a contiguous buffer
+
+
+class Guarded:
+    """a [rows, width] view (leading dimension ld) inside a [rows + 2G, ld] allocation, or a
+    contiguous n-element view inside n + 2 G1 elements (ld = None)"""
+
+    def __init__(self, dev, dtype, fill, rows, width=None, ld=None):
+        self.ld = ld
+        if ld is None:
+            self.alloc = torch.full((rows + 2 * G1,), fill, dtype=dtype, device=dev)
+            self.view = self.alloc[G1:G1 + rows]
+        else:
+            self.alloc = torch.full((rows + 2 * G, ld), fill, dtype=dtype, device=dev)
+            self.view = self.alloc[G:G + rows, :width]
+        self.canary = self.alloc.clone()
+
+    def _bits(self, t):
+        return t.view({2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
+
+    def refill(self):
+        self.alloc.copy_(self.canary)
+
+    def guards_intact(self):
+        """everything outside the view is bit-identical to the canary"""
+        a, c = self._bits(self.alloc).clone(), self._bits(self.canary).clone()
+        for t in (a, c):
+            if self.ld is None:
+                t[G1:G1 + self.view.shape[0]] = 0
+            else:
+                t[G:G + self.view.shape[0], :self.view.shape[1]] = 0
+        return torch.equal(a, c)
+
+
+def guarded_input(dev, data, ld=None):
+    """data (CPU) copied into a NaN-surrounded device buffer -> the view"""
+    if ld is None:
+        g = Guarded(dev, data.dtype, float("nan"), data.numel())
+        g.view.copy_(data.reshape(-1))
+        return g.view.view(data.shape)
+    g = Guarded(dev, data.dtype, float("nan"), data.shape[0], data.shape[1], ld)
+    g.view.copy_(data)
+    return g.view
+
+
+def out_buf(dev, dtype, *shape):
+    n = 1
+    for s in shape:
+        n *= s
+    g = Guarded(dev, dtype, NAN, n)
+    return g, g.view.view(*shape)
+
+
+def check_written(bufs, fails, tag):
+    for name, g in bufs.items():
+        if not g.guards_intact():
+            fails.append(f"{tag} {name}: a guard element was written")
+        if not torch.isfinite(g.view.float()).all():
+            fails.append(f"{tag} {name}: live region not finite (unwritten or poisoned)")
+
+
+def probe_keep(k, dev, M, N, p, seed, batch=1):
+    """the keep bits of the BIAS_DROP_RES epilogue, from the epilogue itself: A = 0 (K = 64),
+    bias = 1, residual 0 -> C is exactly 1/(1-p) (kept) or 0 (dropped); [batch * M, N] bool"""
+    A = torch.zeros(batch * M, 64, dtype=bf16, device=dev)
+    Bm = torch.zeros(batch * N, 64, dtype=bf16, device=dev)
+    bias = torch.ones(N, device=dev)
+    Z = torch.zeros(batch * M, N, dtype=bf16, device=dev)
+    C = torch.full((batch * M, N), NAN, dtype=bf16, device=dev)
+    k.gemm(A, 64, True, Bm, 64, True, C, N, M, N, 64, batch=batch, sA=M * 64, sB=N * 64, sC=M * N,
+           epi=k.epilogue(k.EPI_BIAS_DROP_RES, bias=bias, residual=Z, res_bstride=M * N, drop_p=p, seed=seed))
+    kept = bf16_of(1.0 / (1.0 - p)) if p > 0 else 1.0
+    assert ((C == 0) | (C.float() == kept)).all(), "probe GEMM: an output is neither 0 nor 1/(1-p)"
+    return C != 0
+
+
+def bf16_of(x):
+    return torch.tensor(x, dtype=torch.float32).to(bf16).float().item()

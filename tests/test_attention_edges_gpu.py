@@ -47,11 +47,10 @@ import pytest
 import torch
 
 import attn_harness as H
+from guarded import Guarded, guarded_input
 
 pytestmark = pytest.mark.gpu
 
-G = 2          # guard rows on each side of a 2-D buffer
-G1 = 8         # guard elements on each side of a contiguous buffer
 KEEP_CANARY = 0x5A5A5A5A5A5A5A5A
 
 LENGTHS = [1, 8, 9, 16, 17, 32, 33, 40, 41, 48, 49, 63, 64, 65, 96, 97, 127, 128, 129, 160, 192, 193, 255, 256, 257,
@@ -67,48 +66,6 @@ def K():
 
 
 # ------------------------------------------------------------------------------ buffers
-class Guarded:
-    """a [rows, width] view (leading dimension ld) inside a [rows + 2G, ld] allocation, or a
-    contiguous n-element view inside n + 2 G1 elements (ld = None)"""
-
-    def __init__(self, dev, dtype, fill, rows, width=None, ld=None):
-        self.ld = ld
-        if ld is None:
-            self.alloc = torch.full((rows + 2 * G1,), fill, dtype=dtype, device=dev)
-            self.view = self.alloc[G1:G1 + rows]
-        else:
-            self.alloc = torch.full((rows + 2 * G, ld), fill, dtype=dtype, device=dev)
-            self.view = self.alloc[G:G + rows, :width]
-        self.canary = self.alloc.clone()
-
-    def _bits(self, t):
-        return t.view({2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
-
-    def refill(self):
-        self.alloc.copy_(self.canary)
-
-    def guards_intact(self):
-        """everything outside the view is bit-identical to the canary"""
-        a, c = self._bits(self.alloc).clone(), self._bits(self.canary).clone()
-        for t in (a, c):
-            if self.ld is None:
-                t[G1:G1 + self.view.shape[0]] = 0
-            else:
-                t[G:G + self.view.shape[0], :self.view.shape[1]] = 0
-        return torch.equal(a, c)
-
-
-def guarded_input(dev, data, ld=None):
-    """data (CPU) copied into a NaN-surrounded device buffer -> the view"""
-    if ld is None:
-        g = Guarded(dev, data.dtype, float("nan"), data.numel())
-        g.view.copy_(data.reshape(-1))
-        return g.view.view(data.shape)
-    g = Guarded(dev, data.dtype, float("nan"), data.shape[0], data.shape[1], ld)
-    g.view.copy_(data)
-    return g.view
-
-
 class Buffers:
     """the outputs of one forward + backward, canary-filled"""
 
