@@ -132,6 +132,21 @@ int mmu_gemm(const void* A, int64_t lda, int a_kmajor,
              int64_t batch, int64_t strideA, int64_t strideB, int64_t strideC,
              const mmu_epilogue* epi, mmu_stream_t stream);
 
+/* mmu_gemm whose dropout stream (BIAS_DROP_RES / BIAS_DROP_QGELU) is row-stepped: row m of the
+ * (batched: z*M + m) output draws the decisions of row drop_row_offset + m * drop_row_step of a
+ * dense [.., N] product, i.e. element (m, n) uses counter (drop_row_offset + m*drop_row_step)*N + n.
+ * A compact problem holding every drop_row_step-th row of a dense one (the [CLS] rows of the last
+ * encoder layer: row i = dense row i*L) thus drops exactly what the dense run drops there.  Nothing
+ * but the counter changes; the seed offset of graph replays (mmu_set_seed_offset) is folded in as
+ * in mmu_gemm.  drop_row_step >= 1, drop_row_offset >= 0; (1, 0) is mmu_gemm. */
+int mmu_gemm_rows(const void* A, int64_t lda, int a_kmajor,
+                  const void* B, int64_t ldb, int b_kmajor,
+                  void* C, int64_t ldc, int c_dtype,
+                  int64_t M, int64_t N, int64_t K,
+                  int64_t batch, int64_t strideA, int64_t strideB, int64_t strideC,
+                  const mmu_epilogue* epi, int64_t drop_row_step, int64_t drop_row_offset,
+                  mmu_stream_t stream);
+
 /* Sum `parts` rows of a [parts, N] f32 partial table into out[N] (+= if accumulate). */
 int mmu_colsum_reduce(const float* partial, int64_t parts, int64_t N, float* out,
                       int accumulate, mmu_stream_t stream);
@@ -186,6 +201,31 @@ int mmu_attention_bwd(const void* QKV, int64_t ld_qkv, const float* keymask,
                       float drop_p, uint64_t seed, const uint64_t* dropmask, float* dbias_parts,
                       mmu_stream_t stream);
 
+/* Query row 0 only (the [CLS]-pooled model reads token 0 of its last encoder layer alone,
+ * src/mmbt.py:124-128): the attention of query row 0 of every (batch, head) over all L keys.
+ * Arguments and buffer layouts as mmu_attention_fwd / _bwd; QKV, O, dO, dQKV 16-B aligned, every
+ * ld a multiple of 8.  The Q columns of QKV are read in row 0 of each batch item only.
+ * Forward: writes O row 0 (per batch item: row b*L), LSE[bh][0] and, with drop_p > 0 and a
+ * dropmask, the keep words [bh][0][0..ceil(L/64)) -- the addresses, values and dropout decisions
+ * mmu_attention_fwd produces for that row (same seed, same stream); nothing else is written. */
+int mmu_attention_row0_fwd(const void* QKV, int64_t ld_qkv, const float* keymask,
+                           void* O, int64_t ld_o, float* LSE,
+                           int64_t batch, int64_t L, int64_t heads,
+                           float drop_p, uint64_t seed, uint64_t* dropmask, mmu_stream_t stream);
+/* Backward for a dO that is non-zero in row 0 of each batch item only: reads row 0 of dO, O, LSE
+ * and of the keep words (dropmask required when drop_p > 0); writes the dK and dV columns of dQKV
+ * for ALL rows and the dQ columns of row 0 only (the dQ columns of the other rows -- zeros in the
+ * dense result -- are left untouched).
+ * dbias_sums (may be NULL): f32 [3][batch][heads*64], every element written: per batch item the
+ * column sums over its rows of dQ (slab 0: dQ row 0 itself), dK (slab 1) and dV (slab 2); summing
+ * each slab over the batch (mmu_colsum_reduce, parts = batch) gives the Q / K / V bias gradients. */
+int mmu_attention_row0_bwd(const void* QKV, int64_t ld_qkv, const float* keymask,
+                           const void* O, int64_t ld_o, const void* dO, int64_t ld_do,
+                           const float* LSE, void* dQKV, int64_t ld_dqkv,
+                           int64_t batch, int64_t L, int64_t heads,
+                           float drop_p, const uint64_t* dropmask, float* dbias_sums,
+                           mmu_stream_t stream);
+
 /* ------------------------------------------------------------------ LayerNorm
  * y = LN(x) * w + b over the last dim (768), eps; x, y bf16 [rows, H]; saves
  * mean/rstd f32 [rows].  BertLayerNorm of BertSelfOutput / BertOutput
@@ -219,6 +259,14 @@ int mmu_layernorm_bwd_f32(const void* dY, const float* X, const float* mean, con
                           const float* w, void* dX, void* dXdrop, float drop_p, uint64_t seed,
                           float* part_dw, float* part_db, float* part_dbias,
                           int64_t rows, int64_t H, int64_t rows_per_part, mmu_stream_t stream);
+
+/* mmu_layernorm_bwd_f32 with a row-stepped dropout stream (see mmu_gemm_rows): row r of dXdrop
+ * draws the decisions of row drop_row_offset + r * drop_row_step; (1, 0) is mmu_layernorm_bwd_f32. */
+int mmu_layernorm_bwd_f32_rows(const void* dY, const float* X, const float* mean, const float* rstd,
+                               const float* w, void* dX, void* dXdrop, float drop_p, uint64_t seed,
+                               float* part_dw, float* part_db, float* part_dbias,
+                               int64_t rows, int64_t H, int64_t rows_per_part,
+                               int64_t drop_row_step, int64_t drop_row_offset, mmu_stream_t stream);
 
 /* Pre-LN block backward (FLAVA ResidualAttentionBlock, src/model.py:210-212: x + f(LN(x))):
  * dX = LN'(dY) + dRes; part_dbias = column sums of that total dX (the bias gradient of the

@@ -916,4 +916,229 @@ void attention_bwd_launch(const AttnParams& p, hipStream_t s) {
     hipLaunchKernelGGL(attn_dkdv_dma_kernel<false>, dim3((p.L + 63) / 64, p.batch * p.heads), dim3(128), 0, s, p);
 }
 
+// ------------------------------------------------------------------ query row 0 only
+// The [CLS]-pooled model reads token 0 of its last encoder layer alone (src/mmbt.py:124-128), so
+// that layer's attention is one query row per (batch, head) over all L keys: 2 x 64 x L flops
+// against 256 L bytes of K | V -- memory-bound, all f32 VALU, no MFMA.  One workgroup of 256 per
+// (batch, head): lane (g = t >> 3, c = t & 7) takes keys g, g + 32, ... and the 16-B chunk c of
+// their K / V rows (8 lanes cover one 128-B row).  O, LSE and the keep words of row 0 go where
+// attn_fwd_v2_kernel writes them, with its dropout stream; no other row is touched.
+constexpr int R0_GROUPS = 32;
+
+static __device__ __forceinline__ void ld8f(const bf16* p, float (&o)[8]) {
+  const uint4 u = *(const uint4*)p;
+  const bf16x8 v = *(const bf16x8*)&u;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o[j] = bf2f(v[j]);
+}
+static __device__ __forceinline__ float dot8(const float (&a)[8], const float (&b)[8]) {
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) s = fmaf(a[j], b[j], s);
+  return s;
+}
+static __device__ __forceinline__ float sum8(float v) {  // over the 8 lanes of a key's row
+  v += __shfl_xor(v, 1, 64);
+  v += __shfl_xor(v, 2, 64);
+  v += __shfl_xor(v, 4, 64);
+  return v;
+}
+// sum / max over the 4 waves of the workgroup through red[4] (every thread gets the result)
+template <bool MAX>
+static __device__ __forceinline__ float block_red(float v, float* red, int t) {
+  v = MAX ? wave_max(v) : wave_sum(v);
+  __syncthreads();  // red is free of its last use (and the caller's LDS writes are visible after)
+  if ((t & 63) == 0) red[t >> 6] = v;
+  __syncthreads();
+  return MAX ? fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])) : (red[0] + red[1]) + (red[2] + red[3]);
+}
+// pair_draw with a run-time pair index (one key per lane here, not 16 per lane)
+static __device__ __forceinline__ uint32_t pair_draw_rt(uint32_t hb, int i) {
+  uint32_t mul = kDropMul24[0];
+#pragma unroll
+  for (int e = 1; e < 8; ++e) mul = i == e ? kDropMul24[e] : mul;
+  const uint32_t x = __umul24(__builtin_amdgcn_alignbit(hb, hb, 4 * i), mul);  // rotr(hb, 4i)
+  return x ^ (x >> 16);
+}
+
+template <bool DROP>
+__global__ __launch_bounds__(256) void attn_row0_fwd_kernel(AttnParams p) {
+  __shared__ float sp[FWD_MAX_NKV * 64];  // scores, then the dropped unnormalised probabilities
+  __shared__ float part[R0_GROUPS][64];
+  __shared__ float red[4];
+  const int t = threadIdx.x, c = t & 7, g = t >> 3;
+  const int bh = blockIdx.x, b = bh / p.heads, hd = bh - b * p.heads;
+  const int L = p.L, HD = p.heads * 64, nkv = (L + 63) / 64;
+  // chunk c of this head's q (token 0); K rows at + HD, V rows at + 2 HD
+  const bf16* rows = p.qkv + (int64_t)b * L * p.ld_qkv + hd * 64 + 8 * c;
+  const float* mask = p.keymask + (int64_t)b * L;
+  float q[8];
+  ld8f(rows, q);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) q[j] *= 0.125f;
+  // (four rows' loads in flight per step; unrolled by hand: the lane exchange of sum8 keeps the
+  // compiler from unrolling a loop with a run-time trip count)
+  for (int k0 = g; k0 < L; k0 += 4 * R0_GROUPS) {
+    float kk[4][8];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int k = k0 + R0_GROUPS * u;
+      ld8f(rows + (int64_t)(k < L ? k : 0) * p.ld_qkv + HD, kk[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int k = k0 + R0_GROUPS * u;
+      const float s = sum8(dot8(q, kk[u]));
+      if (c == 0 && k < L) sp[k] = s + mask[k];
+    }
+  }
+  __syncthreads();
+  float mx = NEG_INF;
+  for (int k = t; k < L; k += 256) mx = fmaxf(mx, sp[k]);
+  mx = block_red<true>(mx, red, t);
+  // exponentials, the row sum (before dropout) and the keep decisions: wave w of round r takes
+  // key tile j = 4 r + w, one key per lane, so the tile's keep word is one ballot.  The stream is
+  // attn_fwd_v2_kernel's for q = 0: counter seed_bh + 4 j + 2 h + s2 per 16 keys (key offset
+  // 32 s2 + 16 h + r in the tile), pair r >> 1 of its hash, low / high 16 bits by key parity
+  const uint32_t thr = drop_thr(p.drop_p);
+  const uint32_t ctr = DROP ? seed_for(mmu_eff_seed(p.seed, p.seed_off), bh) : 0u;
+  float ls = 0.f;
+  for (int k = t; (k >> 6) < nkv; k += 256) {  // (k >> 6 is wave-uniform)
+    const int j = k >> 6, ko = k & 63;
+    float e = 0.f;
+    if (k < L) {
+      e = __builtin_amdgcn_exp2f((sp[k] - mx) * LOG2E);
+      ls += e;
+    }
+    if (DROP) {
+      const int s2 = ko >> 5, h = (ko >> 4) & 1;
+      const uint32_t hsh = pair_draw_rt(lowbias32(ctr + 4u * (uint32_t)j + 2u * (uint32_t)h + (uint32_t)s2), (ko & 15) >> 1);
+      bool keep = (ko & 1) ? hsh >= (thr << 16) : (hsh & 0xFFFFu) >= thr;
+      // (the dense kernel skips the second 32-key half of a last tile without a live key: zero bits)
+      if (s2 == 1 && L - 64 * j <= 32) keep = false;
+      const uint64_t word = __ballot(keep);
+      if (p.dropmask && ko == 0) p.dropmask[(int64_t)bh * L * nkv + j] = word;
+      if (!keep) e = 0.f;
+    }
+    if (k < L) sp[k] = e;
+  }
+  ls = block_red<false>(ls, red, t);
+  float acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+#pragma unroll 4
+  for (int k = g; k < L; k += R0_GROUPS) {
+    float v[8];
+    ld8f(rows + (int64_t)k * p.ld_qkv + 2 * HD, v);
+    const float pk = sp[k];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = fmaf(pk, v[j], acc[j]);
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) part[g][8 * c + j] = acc[j];
+  __syncthreads();
+  if (t < 64) {
+    float o = 0.f;
+    for (int gg = 0; gg < R0_GROUPS; ++gg) o += part[gg][t];
+    const float inv = (DROP ? 1.0f / (1.0f - p.drop_p) : 1.0f) / ls;
+    p.out[(int64_t)b * L * p.ld_out + hd * 64 + t] = f2bf(o * inv);
+  }
+  if (t == 0) p.lse[(int64_t)bh * L] = mx + logf(ls);
+}
+
+// Backward of the same row: dO and O of token 0, the forward's LSE and keep words of row 0 ->
+// dK / dV columns of dQKV for every key row, the dQ column of row 0 (no other dQ row is written),
+// and (p.colsum, optional) the column sums [3][batch][heads * 64] of dQ | dK | dV per batch item.
+//   p_k = exp(q k_k / 8 + mask_k - lse), pd_k = keep_k p_k / (1 - p_drop), delta = dO . O,
+//   dV_k = pd_k dO,  dS_k = pd_k (dO . v_k) - p_k delta,  dK_k = dS_k q / 8,  dQ = sum_k dS_k k_k / 8
+template <bool DROP>
+__global__ __launch_bounds__(256) void attn_row0_bwd_kernel(AttnParams p) {
+  __shared__ float part[R0_GROUPS][64];
+  __shared__ float red[4];
+  __shared__ uint64_t kw[FWD_MAX_NKV];
+  const int t = threadIdx.x, c = t & 7, g = t >> 3;
+  const int bh = blockIdx.x, b = bh / p.heads, hd = bh - b * p.heads;
+  const int L = p.L, HD = p.heads * 64, nkv = (L + 63) / 64;
+  const bf16* rows = p.qkv + (int64_t)b * L * p.ld_qkv + hd * 64 + 8 * c;
+  bf16* drows = p.out + (int64_t)b * L * p.ld_out + hd * 64 + 8 * c;
+  const bf16* do0 = p.dout + (int64_t)b * L * p.ld_do + hd * 64;
+  const float* mask = p.keymask + (int64_t)b * L;
+  float q[8], dO[8], o[8];
+  ld8f(rows, q);
+  ld8f(do0 + 8 * c, dO);
+  ld8f(p.o + (int64_t)b * L * p.ld_o + hd * 64 + 8 * c, o);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) q[j] *= 0.125f;
+  const float delta = sum8(dot8(dO, o));
+  const float nlse2 = -p.lse[(int64_t)bh * L] * LOG2E;
+  const float zs = DROP ? 1.0f / (1.0f - p.drop_p) : 1.0f;
+  if (DROP && t < nkv) kw[t] = p.dropmask[(int64_t)bh * L * nkv + t];
+  __syncthreads();
+  float dq[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) dq[j] = 0.f;
+  float sds = 0.f, spd = 0.f;  // sum_k dS_k, sum_k pd_k (the same in the 8 lanes of a row)
+  for (int k0 = g; k0 < L; k0 += 2 * R0_GROUPS) {  // (two rows per step, unrolled by hand as in the forward)
+    float kk2[2][8], v2[2][8];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int k = k0 + R0_GROUPS * u;
+      ld8f(rows + (int64_t)(k < L ? k : 0) * p.ld_qkv + HD, kk2[u]);
+      ld8f(rows + (int64_t)(k < L ? k : 0) * p.ld_qkv + 2 * HD, v2[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int k = k0 + R0_GROUPS * u;
+      const float(&kk)[8] = kk2[u];
+      const float s = sum8(dot8(q, kk)), dp = sum8(dot8(dO, v2[u]));
+      if (k < L) {  // (after the lane exchanges; uniform over the 8 lanes of the row)
+        const float pr = __builtin_amdgcn_exp2f(fmaf(s + mask[k], LOG2E, nlse2));
+        const bool keep = !DROP || ((kw[k >> 6] >> (k & 63)) & 1ull);
+        const float pd = keep ? pr * zs : 0.f;
+        const float ds = fmaf(pd, dp, -pr * delta);
+        bf16x8 ok, ov;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          ok[j] = f2bf(ds * q[j]);
+          ov[j] = f2bf(pd * dO[j]);
+          dq[j] = fmaf(ds, kk[j], dq[j]);
+        }
+        *(bf16x8*)(drows + (int64_t)k * p.ld_out + HD) = ok;
+        *(bf16x8*)(drows + (int64_t)k * p.ld_out + 2 * HD) = ov;
+        sds += ds;
+        spd += pd;
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) part[g][8 * c + j] = dq[j];
+  sds = block_red<false>(c == 0 ? sds : 0.f, red, t);
+  spd = block_red<false>(c == 0 ? spd : 0.f, red, t);
+  if (t < 64) {
+    float v = 0.f;
+    for (int gg = 0; gg < R0_GROUPS; ++gg) v += part[gg][t];
+    v *= 0.125f;
+    p.out[(int64_t)b * L * p.ld_out + hd * 64 + t] = f2bf(v);
+    if (p.colsum) {
+      const int64_t slab = (int64_t)p.batch * HD, at = (int64_t)b * HD + hd * 64 + t;
+      const float qt = bf2f(p.qkv[(int64_t)b * L * p.ld_qkv + hd * 64 + t]) * 0.125f;
+      p.colsum[at] = v;
+      p.colsum[slab + at] = sds * qt;
+      p.colsum[2 * slab + at] = spd * bf2f(do0[t]);
+    }
+  }
+}
+
+void attention_row0_fwd_launch(const AttnParams& p, hipStream_t s) {
+  const dim3 grid(p.batch * p.heads);
+  if (drop_thr(p.drop_p)) hipLaunchKernelGGL(attn_row0_fwd_kernel<true>, grid, dim3(256), 0, s, p);
+  else hipLaunchKernelGGL(attn_row0_fwd_kernel<false>, grid, dim3(256), 0, s, p);
+}
+
+void attention_row0_bwd_launch(const AttnParams& p, hipStream_t s) {
+  const dim3 grid(p.batch * p.heads);
+  if (drop_thr(p.drop_p)) hipLaunchKernelGGL(attn_row0_bwd_kernel<true>, grid, dim3(256), 0, s, p);
+  else hipLaunchKernelGGL(attn_row0_bwd_kernel<false>, grid, dim3(256), 0, s, p);
+}
+
 }  // namespace mmu

@@ -124,9 +124,11 @@ int mmu_timing_read(double* total_ms, int64_t* launches, double* flops) {
   return 0;
 }
 
-int mmu_gemm(const void* A, int64_t lda, int a_kmajor, const void* B, int64_t ldb, int b_kmajor, void* C,
-             int64_t ldc, int c_dtype, int64_t M, int64_t N, int64_t K, int64_t batch, int64_t strideA,
-             int64_t strideB, int64_t strideC, const mmu_epilogue* epi, mmu_stream_t stream) {
+// mmu_gemm / mmu_gemm_rows: the dropout counter of row m is that of row drop_row_off + m drop_row_step
+static int gemm_impl(const void* A, int64_t lda, int a_kmajor, const void* B, int64_t ldb, int b_kmajor, void* C,
+                     int64_t ldc, int c_dtype, int64_t M, int64_t N, int64_t K, int64_t batch, int64_t strideA,
+                     int64_t strideB, int64_t strideC, const mmu_epilogue* epi, int64_t drop_row_step,
+                     int64_t drop_row_off, mmu_stream_t stream) {
   if (!A || !B || !C) return fail("mmu_gemm: null operand");
   if (M <= 0 || N <= 0 || K <= 0 || batch <= 0) return fail("mmu_gemm: bad shape M=%ld N=%ld K=%ld", M, N, K);
   if (N % 128) return fail("mmu_gemm: N=%ld must be a multiple of 128", N);
@@ -138,6 +140,7 @@ int mmu_gemm(const void* A, int64_t lda, int a_kmajor, const void* B, int64_t ld
   p.A = (const bf16*)A; p.B = (const bf16*)B; p.C = C;
   p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.M = M; p.N = N; p.K = K;
   p.sA = strideA; p.sB = strideB; p.sC = strideC;
+  p.drop_ldn = N * drop_row_step; p.drop_base = N * drop_row_off;
   // big (256x256, LDS-DMA) tiling needs >= 256 rows/cols and 32-bit buffer offsets per operand
   // (spans include the rows a 256-tile / 64-deep K-tile may address past the end, so the
   // 32-bit buffer offsets of those out-of-range reads never wrap back into the operand)
@@ -336,6 +339,22 @@ int mmu_gemm(const void* A, int64_t lda, int a_kmajor, const void* B, int64_t ld
   return check_launch("mmu_gemm");
 }
 
+int mmu_gemm(const void* A, int64_t lda, int a_kmajor, const void* B, int64_t ldb, int b_kmajor, void* C,
+             int64_t ldc, int c_dtype, int64_t M, int64_t N, int64_t K, int64_t batch, int64_t strideA,
+             int64_t strideB, int64_t strideC, const mmu_epilogue* epi, mmu_stream_t stream) {
+  return gemm_impl(A, lda, a_kmajor, B, ldb, b_kmajor, C, ldc, c_dtype, M, N, K, batch, strideA, strideB, strideC, epi,
+                   1, 0, stream);
+}
+
+int mmu_gemm_rows(const void* A, int64_t lda, int a_kmajor, const void* B, int64_t ldb, int b_kmajor, void* C,
+                  int64_t ldc, int c_dtype, int64_t M, int64_t N, int64_t K, int64_t batch, int64_t strideA,
+                  int64_t strideB, int64_t strideC, const mmu_epilogue* epi, int64_t drop_row_step,
+                  int64_t drop_row_offset, mmu_stream_t stream) {
+  if (drop_row_step < 1 || drop_row_offset < 0) return fail("mmu_gemm_rows: drop_row_step >= 1, drop_row_offset >= 0");
+  return gemm_impl(A, lda, a_kmajor, B, ldb, b_kmajor, C, ldc, c_dtype, M, N, K, batch, strideA, strideB, strideC, epi,
+                   drop_row_step, drop_row_offset, stream);
+}
+
 int mmu_transpose_bf16_batched(const int64_t* jobs, int n_jobs, int64_t max_rows, int64_t max_cols,
                                mmu_stream_t stream) {
   if (!jobs || n_jobs <= 0 || n_jobs > 65535 || max_rows <= 0 || max_cols <= 0)
@@ -421,6 +440,44 @@ int mmu_attention_bwd(const void* QKV, int64_t ld_qkv, const float* keymask, con
   return check_launch("mmu_attention_bwd");
 }
 
+int mmu_attention_row0_fwd(const void* QKV, int64_t ld_qkv, const float* keymask, void* O, int64_t ld_o, float* LSE,
+                           int64_t batch, int64_t L, int64_t heads, float drop_p, uint64_t seed, uint64_t* dropmask,
+                           mmu_stream_t stream) {
+  if (!QKV || !keymask || !O || !LSE) return fail("mmu_attention_row0_fwd: null pointer");
+  if (attn_common(ld_qkv, batch, L, heads, drop_p)) return 1;
+  if (ld_o < heads * 64 || ld_o % 8) return fail("mmu_attention_row0_fwd: bad ld_o");
+  if (((uintptr_t)QKV | (uintptr_t)O) & 15) return fail("mmu_attention_row0_fwd: QKV / O must be 16-B aligned");
+  AttnParams p{};
+  p.qkv = (const bf16*)QKV; p.ld_qkv = ld_qkv; p.keymask = keymask; p.out = (bf16*)O; p.ld_out = ld_o;
+  p.lse = LSE; p.batch = (int)batch; p.L = (int)L; p.heads = (int)heads; p.drop_p = drop_p; p.seed = seed;
+  p.seed_off = g_seed_off;
+  p.dropmask = dropmask;
+  attention_row0_fwd_launch(p, (hipStream_t)stream);
+  return check_launch("mmu_attention_row0_fwd");
+}
+
+int mmu_attention_row0_bwd(const void* QKV, int64_t ld_qkv, const float* keymask, const void* O, int64_t ld_o,
+                           const void* dO, int64_t ld_do, const float* LSE, void* dQKV, int64_t ld_dqkv,
+                           int64_t batch, int64_t L, int64_t heads, float drop_p, const uint64_t* dropmask,
+                           float* dbias_sums, mmu_stream_t stream) {
+  if (!QKV || !keymask || !O || !dO || !LSE || !dQKV) return fail("mmu_attention_row0_bwd: null pointer");
+  if ((uint32_t)(drop_p * 65536.0f + 0.5f) != 0 && !dropmask)
+    return fail("mmu_attention_row0_bwd: dropout needs the forward's dropmask");
+  if (attn_common(ld_qkv, batch, L, heads, drop_p)) return 1;
+  if (ld_dqkv < 3 * heads * 64 || ld_do < heads * 64 || ld_o < heads * 64 || ld_do % 8 || ld_o % 8 || ld_dqkv % 8)
+    return fail("mmu_attention_row0_bwd: bad ld");
+  if (((uintptr_t)QKV | (uintptr_t)O | (uintptr_t)dO | (uintptr_t)dQKV) & 15)
+    return fail("mmu_attention_row0_bwd: QKV / O / dO / dQKV must be 16-B aligned");
+  AttnParams p{};
+  p.qkv = (const bf16*)QKV; p.ld_qkv = ld_qkv; p.keymask = keymask; p.o = (const bf16*)O; p.ld_o = ld_o;
+  p.dout = (const bf16*)dO; p.ld_do = ld_do; p.lse = (float*)LSE; p.out = (bf16*)dQKV;
+  p.ld_out = ld_dqkv; p.batch = (int)batch; p.L = (int)L; p.heads = (int)heads; p.drop_p = drop_p;
+  p.dropmask = (uint64_t*)dropmask;
+  p.colsum = dbias_sums;
+  attention_row0_bwd_launch(p, (hipStream_t)stream);
+  return check_launch("mmu_attention_row0_bwd");
+}
+
 int mmu_layernorm_fwd(const void* X, const float* w, const float* b, void* Y, float* mean, float* rstd, int64_t rows,
                       int64_t H, float eps, int64_t group_rows, int64_t param_stride, mmu_stream_t stream) {
   if (!X || !w || !b || !Y) return fail("mmu_layernorm_fwd: null pointer");
@@ -466,6 +523,22 @@ int mmu_layernorm_bwd_f32(const void* dY, const float* X, const float* mean, con
   layernorm_bwd_launch((const bf16*)dY, X, true, mean, rstd, w, (bf16*)dX, (bf16*)dXdrop, nullptr, drop_p, seed,
                        g_seed_off, part_dw, part_db, part_dbias, rows, H, rows_per_part, (hipStream_t)stream);
   return check_launch("mmu_layernorm_bwd_f32");
+}
+
+int mmu_layernorm_bwd_f32_rows(const void* dY, const float* X, const float* mean, const float* rstd, const float* w,
+                               void* dX, void* dXdrop, float drop_p, uint64_t seed, float* part_dw, float* part_db,
+                               float* part_dbias, int64_t rows, int64_t H, int64_t rows_per_part,
+                               int64_t drop_row_step, int64_t drop_row_offset, mmu_stream_t stream) {
+  if (!dY || !X || !mean || !rstd || !w || !dX) return fail("mmu_layernorm_bwd_f32_rows: null pointer");
+  if (rows <= 0 || H <= 0 || H % 256 || H > 1024 || rows_per_part <= 0)
+    return fail("mmu_layernorm_bwd_f32_rows: bad shape");
+  if (drop_p < 0.f || drop_p >= 1.f) return fail("mmu_layernorm_bwd_f32_rows: drop_p out of range");
+  if (drop_row_step < 1 || drop_row_offset < 0)
+    return fail("mmu_layernorm_bwd_f32_rows: drop_row_step >= 1, drop_row_offset >= 0");
+  layernorm_bwd_launch((const bf16*)dY, X, true, mean, rstd, w, (bf16*)dX, (bf16*)dXdrop, nullptr, drop_p, seed,
+                       g_seed_off, part_dw, part_db, part_dbias, rows, H, rows_per_part, (hipStream_t)stream,
+                       drop_row_step, drop_row_offset);
+  return check_launch("mmu_layernorm_bwd_f32_rows");
 }
 
 int mmu_layernorm_bwd_res(const void* dY, const void* X, const float* mean, const float* rstd, const float* w,

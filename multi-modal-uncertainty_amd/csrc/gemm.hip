@@ -231,7 +231,8 @@ static __device__ __forceinline__ void epilogue_block(const GemmParams& p, int64
   constexpr bool DRP = EPI == MMU_EPI_BIAS_DROP_RES || EPI == MMU_EPI_BIAS_DROP_QGELU;
   const int64_t x_l = XST ? m_l * p.ldx + n : 0;
   const int64_t s_l = EPI == MMU_EPI_STORE ? m_l * p.N + n : 0;
-  const int64_t q_l = DRP ? (z * p.M + m_l) * p.N + n : 0;
+  // (the dropout counter's row pitch / base: N and 0, or row-stepped -- mmu_gemm_rows)
+  const int64_t q_l = DRP ? p.drop_base + (z * p.M + m_l) * p.drop_ldn + n : 0;
   const uint64_t seed = DRP && thr ? mmu_eff_seed(p.seed, p.seed_off) : 0;
   // residual = LN(residual rows): per-column gamma / beta here, per-row mean / rstd per pass
   const bool res_ln = RES32 && p.res_ln_w != nullptr && !slab;
@@ -346,7 +347,7 @@ static __device__ __forceinline__ void epilogue_block(const GemmParams& p, int64
       }
       void* cdst = OUT_F32 ? (void*)((float*)p.C + c_l + d * p.ldc) : (void*)((bf16*)p.C + c_l + d * p.ldc);
       epi_oct<EPI, OUT_F32>(p, cdst, (XST && aux) ? aux + x_l + d * p.ldx : nullptr,
-                            DRP ? (uint64_t)(q_l + d * p.N) >> 2 : 0, v, inf, scale, thr, seed);
+                            DRP ? (uint64_t)(q_l + d * p.drop_ldn) >> 2 : 0, v, inf, scale, thr, seed);
       if (want_cs) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) cs[e] += v[e];

@@ -224,7 +224,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16* __restrict__ dY
                                                      bf16* __restrict__ dXd, const bf16* __restrict__ dR,
                                                      float drop_p, uint64_t seed, const uint64_t* seed_off,
                                                      float* __restrict__ pdw, float* __restrict__ pdb,
-                                                     float* __restrict__ pdbias, int64_t rows, int rpp) {
+                                                     float* __restrict__ pdbias, int64_t rows, int rpp,
+                                                     int64_t drop_step, int64_t drop_off) {
   constexpr int H = 256 * NV, nv = NV;
   __shared__ float red[4][H];
   const int l = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -286,7 +287,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16* __restrict__ dY
         }
         *(bf16x4*)(dX + row * H + c) = bf16x4{f2bf(dx[0]), f2bf(dx[1]), f2bf(dx[2]), f2bf(dx[3])};
         if (dXd) {
-          uint32_t keep = thr ? mmu_keep4(mmu_eff_seed(seed, seed_off), (uint64_t)(row * H + c) >> 2, thr) : 0xFu;
+          uint32_t keep = thr ? mmu_keep4(mmu_eff_seed(seed, seed_off), (uint64_t)((row * drop_step + drop_off) * H + c) >> 2, thr) : 0xFu;
 #pragma unroll
           for (int e = 0; e < 4; ++e) dx[e] = ((keep >> e) & 1) ? dx[e] * scale : 0.f;
           *(bf16x4*)(dXd + row * H + c) = bf16x4{f2bf(dx[0]), f2bf(dx[1]), f2bf(dx[2]), f2bf(dx[3])};
@@ -368,10 +369,10 @@ template <typename XT>
 static void ln_bwd_launch_t(const bf16* dY, const XT* X, const float* mean, const float* rstd, const float* w,
                             bf16* dX, bf16* dXdrop, const bf16* dR, float drop_p, uint64_t seed,
                             const uint64_t* seed_off, float* pdw, float* pdb, float* pdbias, int64_t rows, int64_t H,
-                            int64_t rpp, hipStream_t s) {
+                            int64_t rpp, hipStream_t s, int64_t dstep, int64_t doff) {
   const dim3 g((unsigned)((rows + rpp - 1) / rpp));
 #define LNB(NV) hipLaunchKernelGGL((ln_bwd_kernel<NV, XT>), g, dim3(256), 0, s, dY, X, mean, rstd, w, dX, dXdrop, dR, \
-                                   drop_p, seed, seed_off, pdw, pdb, pdbias, rows, (int)rpp)
+                                   drop_p, seed, seed_off, pdw, pdb, pdbias, rows, (int)rpp, dstep, doff)
   switch (H / 256) {
     case 1: LNB(1); break;
     case 2: LNB(2); break;
@@ -384,13 +385,14 @@ static void ln_bwd_launch_t(const bf16* dY, const XT* X, const float* mean, cons
 void layernorm_bwd_launch(const bf16* dY, const void* X, bool x_f32, const float* mean, const float* rstd,
                           const float* w, bf16* dX, bf16* dXdrop, const bf16* dR, float drop_p, uint64_t seed,
                           const uint64_t* seed_off, float* pdw, float* pdb, float* pdbias, int64_t rows, int64_t H,
-                          int64_t rpp, hipStream_t s) {
+                          int64_t rpp, hipStream_t s, int64_t dstep, int64_t doff) {
+  // dstep / doff: the dropout counter's row is row * dstep + doff (mmu_layernorm_bwd_f32_rows)
   if (x_f32)
     ln_bwd_launch_t(dY, (const float*)X, mean, rstd, w, dX, dXdrop, dR, drop_p, seed, seed_off, pdw, pdb, pdbias, rows,
-                    H, rpp, s);
+                    H, rpp, s, dstep, doff);
   else
     ln_bwd_launch_t(dY, (const bf16*)X, mean, rstd, w, dX, dXdrop, dR, drop_p, seed, seed_off, pdw, pdb, pdbias, rows,
-                    H, rpp, s);
+                    H, rpp, s, dstep, doff);
 }
 
 }  // namespace mmu

@@ -31,6 +31,10 @@ struct GemmParams {
   float drop_p;
   uint64_t seed;
   const uint64_t* seed_off;  // per-replay seed counter (mmu_set_seed_offset), or NULL
+  // dropout counter of element (z, m, n): drop_base + (z M + m) drop_ldn + n.  mmu_gemm: (0, N);
+  // mmu_gemm_rows: (row_offset N, row_step N) -- row m draws the decisions of row
+  // row_offset + m row_step of a dense [.., N] product
+  int64_t drop_base, drop_ldn;
   // f32 residual = LN(residual rows) recomputed per element (mmu_epilogue res_ln_*)
   const float *res_ln_mean, *res_ln_rstd, *res_ln_w, *res_ln_b;
   int64_t res_ln_bstride;
@@ -110,6 +114,10 @@ struct AttnParams {
 };
 void attention_fwd_launch(const AttnParams& p, hipStream_t s);
 void attention_bwd_launch(const AttnParams& p, hipStream_t s);
+// query row 0 of every (batch, head) only (mmu_attention_row0_fwd / _bwd): p.colsum = the bwd's
+// [3][batch][heads * 64] column sums
+void attention_row0_fwd_launch(const AttnParams& p, hipStream_t s);
+void attention_row0_bwd_launch(const AttnParams& p, hipStream_t s);
 
 void layernorm_fwd_launch(const bf16* X, const float* w, const float* b, bf16* Y, float* mean, float* rstd,
                           int64_t rows, int64_t H, float eps, int64_t group_rows, int64_t pstride, hipStream_t s);
@@ -119,7 +127,7 @@ void layernorm_fwd32_launch(const float* X, const float* w, const float* b, bf16
 void layernorm_bwd_launch(const bf16* dY, const void* X, bool x_f32, const float* mean, const float* rstd,
                           const float* w, bf16* dX, bf16* dXdrop, const bf16* dR, float drop_p, uint64_t seed,
                           const uint64_t* seed_off, float* pdw, float* pdb, float* pdbias, int64_t rows, int64_t H,
-                          int64_t rows_per_part, hipStream_t s);
+                          int64_t rows_per_part, hipStream_t s, int64_t drop_row_step = 1, int64_t drop_row_off = 0);
 
 // FLAVA attention over the sequence (= batch) axis, flava.hip
 struct SeqAttnParams {

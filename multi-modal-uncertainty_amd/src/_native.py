@@ -37,6 +37,14 @@ SIGNATURES = {
     "mmu_set_seed_offset": (c_i32, [c_vp]),
     "mmu_gemm": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_i64, c_i64, c_i64,
                          c_i64, c_i64, c_i64, c_i64, ctypes.POINTER(Epilogue), c_vp]),
+    "mmu_gemm_rows": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_i64, c_i64, c_i64,
+                              c_i64, c_i64, c_i64, c_i64, ctypes.POINTER(Epilogue), c_i64, c_i64, c_vp]),
+    "mmu_attention_row0_fwd": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_f32, c_u64, c_vp,
+                                       c_vp]),
+    "mmu_attention_row0_bwd": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64,
+                                       c_i64, c_i64, c_i64, c_f32, c_vp, c_vp, c_vp]),
+    "mmu_layernorm_bwd_f32_rows": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_u64, c_vp, c_vp, c_vp,
+                                           c_i64, c_i64, c_i64, c_i64, c_i64, c_vp]),
     "mmu_colsum_reduce": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_i32, c_vp]),
     "mmu_colsum_reduce_multi": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp]),
     "mmu_colsum_bf16": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i32, c_vp]),

@@ -114,18 +114,156 @@ def layer_forward(lw, X, R, keymask, B, L, p_attn, p_hid, seeds, save, res_ln=No
     return Y, S2, mean2, rstd2, saved, Y32
 
 
+# The last layer of a [CLS]-pooled stack computes only what token 0 needs (last_layer_forward /
+# last_layer_backward); MMU_LAST_CLS=0: the dense layer, whose [CLS] rows alone are then read.
+LAST_LAYER_CLS = os.environ.get("MMU_LAST_CLS", "1") != "0"
+
+
+def _cls_rows(t, B, L):
+    """rows 0, L, 2L, ... of a [B*L, ...] tensor (or per-row vector), contiguous"""
+    return t.view(B, L, *t.shape[1:])[:, 0].contiguous()
+
+
+def last_layer_forward(lw, X, R, keymask, B, L, p_attn, p_hid, seeds, save, res_ln=None):
+    """The last layer of a stack whose only consumer is the pooler (token 0 of each sequence,
+    src/mmbt.py:124-128): K | V for every row, everything else -- Q, the attention, Wo, LN1, the
+    FFN, LN2 -- for the B [CLS] rows only, as compact [B, .] problems whose hidden-dropout
+    streams are row-stepped by L, so that row b draws what the dense layer draws in row b L.
+    -> (Y32 [B, 768] f32, saved)."""
+    M = B * L
+    dev = X.device
+    f32 = torch.float32
+    qkv = torch.empty(M, 3 * HID, dtype=bf16, device=dev)  # Q columns: the [CLS] rows only
+    K.gemm(X, HID, True, lw.wqkv16[HID:], HID, True, qkv[:, HID:], 3 * HID, M, 2 * HID, HID,
+           epi=K.epilogue(K.EPI_STORE, bias=lw.bqkv[HID:]))
+    Xc = _cls_rows(X, B, L)
+    K.gemm(Xc, HID, True, lw.wqkv16[:HID], HID, True, qkv, L * 3 * HID, B, HID, HID,
+           epi=K.epilogue(K.EPI_STORE, bias=lw.bqkv[:HID]))  # (row pitch L * 2304: into rows b L)
+    # (dense-shaped O / lse / keep words: the kernel writes row 0 of each where the dense one does;
+    # the other rows are never touched, only the compact copies live on)
+    O = torch.empty(M, HID, dtype=bf16, device=dev)
+    lse = torch.empty(B * HEADS, L, dtype=f32, device=dev)
+    dmask = K.dropmask_empty(B, L, HEADS, dev) if (save and p_attn > 0) else None
+    K.attention_row0_fwd(qkv, keymask, O, lse, B, L, HEADS, p_attn, seeds[0], dmask)
+    Oc = _cls_rows(O, B, L)
+    Rc = _cls_rows(R, B, L)
+    if res_ln is not None:
+        res_ln = (_cls_rows(res_ln[0], B, L), _cls_rows(res_ln[1], B, L), res_ln[2], res_ln[3])
+    S1 = torch.empty(B, HID, dtype=f32, device=dev)
+    K.gemm(Oc, HID, True, lw.wo16, HID, True, S1, HID, B, HID, HID,
+           epi=K.epilogue(K.EPI_BIAS_DROP_RES, bias=lw.bo, residual=Rc, drop_p=p_hid, seed=seeds[1], res_ln=res_ln),
+           row_step=L)
+    A = torch.empty(B, HID, dtype=bf16, device=dev)
+    mean1 = torch.empty(B, dtype=f32, device=dev)
+    rstd1 = torch.empty(B, dtype=f32, device=dev)
+    K.layernorm_fwd_f32(S1, lw.ln1w, lw.ln1b, A, None, mean1, rstd1)
+    Z = torch.empty(B, FFN, dtype=bf16, device=dev) if save else None
+    Hh = torch.empty(B, FFN, dtype=bf16, device=dev)
+    K.gemm(A, HID, True, lw.w116, HID, True, Hh, FFN, B, FFN, HID, epi=K.epilogue(K.EPI_BIAS_GELU, bias=lw.b1, aux=Z))
+    S2 = torch.empty(B, HID, dtype=f32, device=dev)
+    K.gemm(Hh, FFN, True, lw.w216, FFN, True, S2, HID, B, HID, FFN,
+           epi=K.epilogue(K.EPI_BIAS_DROP_RES, bias=lw.b2, residual=S1, drop_p=p_hid, seed=seeds[2],
+                          res_ln=(mean1, rstd1, lw.ln1w, lw.ln1b)), row_step=L)
+    Y32 = torch.empty(B, HID, dtype=f32, device=dev)
+    mean2 = torch.empty(B, dtype=f32, device=dev)
+    rstd2 = torch.empty(B, dtype=f32, device=dev)
+    K.layernorm_fwd_f32(S2, lw.ln2w, lw.ln2b, torch.empty(B, HID, dtype=bf16, device=dev), Y32, mean2, rstd2)
+    saved = None
+    if save:
+        saved = (X, Xc, qkv, Oc, lse[:, 0].contiguous(), dmask[:, 0].contiguous() if dmask is not None else None,
+                 S1, mean1, rstd1, A, Z, Hh, S2, mean2, rstd2)
+    return Y32, saved
+
+
+def last_layer_backward(lw, saved, dY32, keymask, B, L, p_attn, p_hid, seeds, wgrad):
+    """dY32 [B, 768]: the gradient of the [CLS] rows.  The row-wise chain (LN2', W2, gelu', W1,
+    LN1', Wo) runs on those B rows; the attention backward has dO in query row 0 only; dX =
+    dK|dV . Wk|v for every row, and the [CLS] rows' full dqkv . Wqkv + dS1 on top.  Weight
+    gradients: B-row products, but the K | V rows of g_wqkv (the dense product)."""
+    X, Xc, qkv, Oc, lse0, kw0, S1, mean1, rstd1, A, Z, Hh, S2, mean2, rstd2 = saved
+    M = B * L
+    dev = dY32.device
+    P = K.ln_parts(B)
+    side = _Side(dev, wgrad)
+    pw = pb = pbias = pw1 = pb1 = pbias1 = None
+    if wgrad:
+        pw, pb, pbias, pw1, pb1, pbias1 = (torch.empty(P, HID, dtype=torch.float32, device=dev) for _ in range(6))
+    acc = K.epilogue(K.EPI_STORE, accumulate=True)
+    dY = dY32.to(bf16).contiguous()
+    # ---- output LayerNorm + dropout + W2
+    dS2 = torch.empty(B, HID, dtype=bf16, device=dev)
+    dY2 = torch.empty(B, HID, dtype=bf16, device=dev)
+    K.layernorm_bwd(dY, S2, mean2, rstd2, lw.ln2w, dS2, dY2, p_hid, seeds[2], pw, pb, pbias, row_step=L)
+    if wgrad:
+        def w2():
+            K.colsum_reduce_multi([(pw, lw.g_ln2w), (pb, lw.g_ln2b), (pbias, lw.g_b2)], accumulate=True)
+            K.gemm(dY2, HID, False, Hh, FFN, False, lw.g_w2, FFN, HID, FFN, B, epi=acc)
+        side.run(w2, pw, pb, pbias, dY2, Hh)
+    dZ = torch.empty(B, FFN, dtype=bf16, device=dev)
+    K.gemm(dY2, HID, True, lw.w2t16, HID, True, dZ, FFN, B, FFN, HID,
+           epi=K.epilogue(K.EPI_DGELU, aux=Z, colsum=lw.g_b1 if wgrad else None))
+    if wgrad:
+        side.run(lambda: K.gemm(dZ, FFN, False, A, HID, False, lw.g_w1, HID, FFN, HID, B, epi=acc), dZ, A)
+    dA = torch.empty(B, HID, dtype=bf16, device=dev)
+    K.gemm(dZ, FFN, True, lw.w1t16, FFN, True, dA, HID, B, HID, FFN, epi=K.epilogue(K.EPI_ADD_RES, residual=dS2))
+    # ---- attention-output LayerNorm + dropout + Wo
+    dS1 = torch.empty(B, HID, dtype=bf16, device=dev)
+    dAo = torch.empty(B, HID, dtype=bf16, device=dev)
+    K.layernorm_bwd(dA, S1, mean1, rstd1, lw.ln1w, dS1, dAo, p_hid, seeds[1], pw1, pb1, pbias1, row_step=L)
+    if wgrad:
+        def wo():
+            K.colsum_reduce_multi([(pw1, lw.g_ln1w), (pb1, lw.g_ln1b), (pbias1, lw.g_bo)], accumulate=True)
+            K.gemm(dAo, HID, False, Oc, HID, False, lw.g_wo, HID, HID, HID, B, epi=acc)
+        side.run(wo, pw1, pb1, pbias1, dAo, Oc)
+    # ---- attention (query row 0) + fused QKV.  The kernel addresses dO / O / lse / the keep
+    # words as the dense ones do: dense-shaped buffers with row 0 of each sequence filled in
+    dO = torch.empty(M, HID, dtype=bf16, device=dev)
+    K.gemm(dAo, HID, True, lw.wot16, HID, True, dO, L * HID, B, HID, HID)  # (row pitch L * 768: rows b L)
+    O = torch.empty(M, HID, dtype=bf16, device=dev)
+    O.view(B, L, HID)[:, 0] = Oc
+    lse = torch.empty(B * HEADS, L, dtype=torch.float32, device=dev)
+    lse[:, 0] = lse0
+    dmask = None
+    if kw0 is not None:
+        dmask = K.dropmask_empty(B, L, HEADS, dev)
+        dmask[:, 0] = kw0
+    dqkv = torch.empty(M, 3 * HID, dtype=bf16, device=dev)  # dQ columns: the [CLS] rows only
+    dbs = K.attention_row0_dbias(B, HEADS, dev) if wgrad else None
+    K.attention_row0_bwd(qkv, keymask, O, dO, lse, dqkv, B, L, HEADS, p_attn, dmask, dbs)
+    dqkv_c = _cls_rows(dqkv, B, L)  # [B, 2304]: the full dQ | dK | dV rows of the [CLS] tokens
+    if wgrad:
+        def wqkv():
+            K.colsum_reduce_multi([(dbs[0], lw.g_bqkv[:HID]), (dbs[1], lw.g_bqkv[HID:2 * HID]),
+                                   (dbs[2], lw.g_bqkv[2 * HID:])], accumulate=True)
+            K.gemm(dqkv[:, HID:], 3 * HID, False, X, HID, False, lw.g_wqkv[HID:], HID, 2 * HID, HID, M, epi=acc)
+            K.gemm(dqkv_c, 3 * HID, False, Xc, HID, False, lw.g_wqkv[:HID], HID, HID, HID, B, epi=acc)
+        side.run(wqkv, dqkv, dqkv_c, X, Xc, dbs)
+    dX = torch.empty(M, HID, dtype=bf16, device=dev)
+    K.gemm(dqkv[:, HID:], 3 * HID, True, lw.wqkvt16[:, HID:], 3 * HID, True, dX, HID, M, HID, 2 * HID)
+    # the [CLS] rows again, whole: dqkv . Wqkv + dS1 as the dense layer forms them (row pitch L * 768)
+    K.gemm(dqkv_c, 3 * HID, True, lw.wqkvt16, 3 * HID, True, dX, L * HID, B, HID, 3 * HID,
+           epi=K.epilogue(K.EPI_ADD_RES, residual=dS1))
+    return dX, side
+
+
 def encoder_stack(lws, X, X32, keymask, B, L, p_attn, p_hid, seeds_of, need_grad, hook=None, all_layers=False,
                   cls_only=False):
     """Run the fused layers over (X bf16, X32 f32 embedding rows); returns the f32 hidden
     state of the last layer, or of every layer (all_layers); with cls_only only the last layer's
     [CLS] rows [B, 768] (the pooler's input: no f32 copy of the other B (L - 1) rows, and no
-    [B L, 768] f32 zero gradient for them in the backward)."""
+    [B L, 768] f32 zero gradient for them in the backward; with LAST_LAYER_CLS that layer computes
+    nothing else)."""
     R, rln, outs = X32, None, []
     n = len(lws)
     for i, lw in enumerate(lws):
         out32 = all_layers or i == n - 1
         if out32 and cls_only and not all_layers:
             out32 = "cls"
+        if out32 == "cls" and LAST_LAYER_CLS:
+            if need_grad:
+                return BertLastLayerFunction.apply(X, R, lw.anchor, lw, keymask, B, L, p_attn, p_hid, seeds_of(i),
+                                                   hook, rln, i == 0)
+            return last_layer_forward(lw, X, R, keymask, B, L, p_attn, p_hid, seeds_of(i), False, rln)[0]
         if need_grad:
             # (layer 0's backward is the encoder's last: it flushes the deferred weight gradients)
             X, R, mu, rs, Y32 = BertLayerFunction.apply(X, R, lw.anchor, lw, keymask, B, L, p_attn, p_hid,
@@ -399,3 +537,40 @@ class BertLayerFunction(torch.autograd.Function):
         return (dX,) + (None,) * 13
 
 
+
+class BertLastLayerFunction(torch.autograd.Function):
+    """The last fused BertLayer of a [CLS]-pooled stack (LAST_LAYER_CLS): X bf16 [B*L, 768] + its
+    f32 residual -> the [CLS] rows' f32 output [B, 768] (last_layer_forward); the layer's whole
+    input gradient is returned for X, as in BertLayerFunction."""
+
+    @staticmethod
+    def forward(ctx, X, R, anchor, lw, keymask, B, L, p_attn, p_hid, seeds, on_grads_ready, res_ln=None,
+                flush=False):
+        ctx.set_materialize_grads(False)
+        e0 = _mark()
+        Y32, saved = last_layer_forward(lw, X, R, keymask, B, L, p_attn, p_hid, seeds, True, res_ln)
+        if e0 is not None:
+            _block_events.append((e0, _mark()))
+        ctx.saved_bufs = saved
+        ctx.meta = (lw, keymask, B, L, p_attn, p_hid, seeds, on_grads_ready, flush)
+        return Y32
+
+    @staticmethod
+    def backward(ctx, dY32):
+        lw, keymask, B, L, p_attn, p_hid, seeds, hook, flush = ctx.meta
+        if dY32 is None:
+            return (None,) * 13
+        wgrad = lw.trainable()
+        e0 = _mark()
+        dX, side = last_layer_backward(lw, ctx.saved_bufs, dY32, keymask, B, L, p_attn, p_hid, seeds, wgrad)
+        if e0 is not None:
+            _block_events.append((e0, _mark()))
+        ctx.saved_bufs = None
+        if wgrad and side.defer:
+            if hook is not None:  # the bucket all-reduce follows the layer's deferred work
+                _defer(side.dev, lambda: hook(lw), ())
+            if flush:
+                _flush_deferred(side.dev, INTERLEAVE)
+        elif wgrad and hook is not None:
+            hook(lw)
+        return (dX,) + (None,) * 12

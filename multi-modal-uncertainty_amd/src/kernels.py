@@ -177,8 +177,11 @@ def join_at_backward_end(main, side):
     torch.autograd.Variable._execution_engine.queue_callback(join)
 
 
-def gemm(A, lda, a_kmajor, B, ldb, b_kmajor, C, ldc, M, N_, K, epi=None, batch=1, sA=0, sB=0, sC=0):
-    """C[m,n] = sum_k A(m,k) B(n,k) (+ fused epilogue); see mmu_gemm in include/mmu.h."""
+def gemm(A, lda, a_kmajor, B, ldb, b_kmajor, C, ldc, M, N_, K, epi=None, batch=1, sA=0, sB=0, sC=0, row_step=None,
+         row_offset=0):
+    """C[m,n] = sum_k A(m,k) B(n,k) (+ fused epilogue); see mmu_gemm in include/mmu.h.
+    row_step (not None: mmu_gemm_rows) / row_offset: the epilogue's dropout decisions of row m are
+    those of row row_offset + m * row_step of a dense product."""
     _dev_check(A, B, C)
     _want(A, torch.bfloat16, "gemm A")
     _want(B, torch.bfloat16, "gemm B")
@@ -192,8 +195,12 @@ def gemm(A, lda, a_kmajor, B, ldb, b_kmajor, C, ldc, M, N_, K, epi=None, batch=1
         epi = type(epi).from_buffer_copy(epi)
         ws = _splitk_workspace(C.device)
         epi.workspace, epi.workspace_floats = ws.data_ptr(), ws.numel()
-    N.call("mmu_gemm", _ptr(A), lda, int(a_kmajor), _ptr(B), ldb, int(b_kmajor), _ptr(C), ldc, cdt, M, N_, K,
-           batch, sA, sB, sC, ctypes.byref(epi) if epi is not None else None, _stream(C))
+    if row_step is not None:
+        N.call("mmu_gemm_rows", _ptr(A), lda, int(a_kmajor), _ptr(B), ldb, int(b_kmajor), _ptr(C), ldc, cdt, M, N_, K,
+               batch, sA, sB, sC, ctypes.byref(epi), int(row_step), int(row_offset), _stream(C))
+    else:
+        N.call("mmu_gemm", _ptr(A), lda, int(a_kmajor), _ptr(B), ldb, int(b_kmajor), _ptr(C), ldc, cdt, M, N_, K,
+               batch, sA, sB, sC, ctypes.byref(epi) if epi is not None else None, _stream(C))
     if _alg["on"]:
         _count_alg(M, N_, K, batch, 4 if cdt == N.MMU_F32 else 2, epi)
     return C
@@ -294,6 +301,54 @@ def attention_bwd(qkv, keymask, O, dO, lse, delta, dqkv, batch, L, heads=12, dro
            _ptr(dropmask) if dropmask is not None else None, _ptr(dbias_parts), _stream(qkv))
 
 
+def _row0_check(who, batch, L, heads, *mats):
+    """[batch * L, >= heads * 64] bf16 matrices with 16-B aligned rows (the C entry checks the pitches)"""
+    for t in mats:
+        _want(t, torch.bfloat16, who)
+        if t.dim() != 2 or t.shape[0] < batch * L or t.shape[1] < heads * 64 or t.stride(1) != 1 \
+                or t.stride(0) % 8 or t.data_ptr() % 16:
+            raise N.NativeError(f"{who}: operands are [batch * L, cols] bf16 with 16-B aligned rows, got "
+                                f"{tuple(t.shape)} strides {t.stride()}")
+
+
+def attention_row0_fwd(qkv, keymask, O, lse, batch, L, heads=12, drop_p=0.0, seed=0, dropmask=None):
+    """attention_fwd for query row 0 of every (batch, head) only: O row 0, lse[:, 0] and the keep
+    words [:, 0] are written exactly where (and as) attention_fwd writes them; nothing else is."""
+    _dev_check(qkv, keymask, O, lse)
+    _row0_check("attention_row0_fwd", batch, L, heads, qkv, O)
+    if dropmask is not None:
+        _dev_check(dropmask)
+        if dropmask.numel() < batch * heads * L * ((L + 63) // 64) or not dropmask.is_contiguous():
+            raise ValueError("attention_row0_fwd: dropmask too small / not contiguous")
+    if lse.numel() < batch * heads * L or keymask.numel() < batch * L:
+        raise ValueError("attention_row0_fwd: lse [batch * heads, L] / keymask [batch, L] too small")
+    N.call("mmu_attention_row0_fwd", _ptr(qkv), qkv.stride(0), _ptr(keymask), _ptr(O), O.stride(0), _ptr(lse), batch,
+           L, heads, float(drop_p), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(dropmask), _stream(qkv))
+
+
+def attention_row0_dbias(batch, heads=12, device=None):
+    """the [3, batch, heads * 64] f32 column sums (dQ | dK | dV per batch item) of attention_row0_bwd"""
+    return torch.empty(3, batch, heads * 64, dtype=torch.float32, device=device)
+
+
+def attention_row0_bwd(qkv, keymask, O, dO, lse, dqkv, batch, L, heads=12, drop_p=0.0, dropmask=None,
+                       dbias_sums=None):
+    """Backward of attention_row0_fwd (dO read in row 0 of each batch item only): the dK | dV
+    columns of dqkv for all rows, its dQ columns in row 0 only; see mmu_attention_row0_bwd."""
+    _dev_check(qkv, keymask, O, dO, lse, dqkv, dbias_sums)
+    _row0_check("attention_row0_bwd", batch, L, heads, qkv, dqkv, O, dO)
+    if dropmask is not None:
+        _dev_check(dropmask)
+        if dropmask.numel() < batch * heads * L * ((L + 63) // 64) or not dropmask.is_contiguous():
+            raise ValueError("attention_row0_bwd: dropmask too small / not contiguous")
+    if dbias_sums is not None and (dbias_sums.dtype != torch.float32 or not dbias_sums.is_contiguous()
+                                   or dbias_sums.numel() < 3 * batch * heads * 64):
+        raise ValueError("attention_row0_bwd: dbias_sums must be contiguous f32 [3, batch, heads * 64]")
+    N.call("mmu_attention_row0_bwd", _ptr(qkv), qkv.stride(0), _ptr(keymask), _ptr(O), O.stride(0), _ptr(dO),
+           dO.stride(0), _ptr(lse), _ptr(dqkv), dqkv.stride(0), batch, L, heads, float(drop_p), _ptr(dropmask),
+           _ptr(dbias_sums), _stream(qkv))
+
+
 LN_ROWS_PER_PART = 64
 
 
@@ -377,14 +432,24 @@ def layernorm_fwd_f32(X, w, b, Y, Y32=None, mean=None, rstd=None, eps=1e-12, gro
 
 
 def layernorm_bwd(dY, X, mean, rstd, w, dX, dXdrop=None, drop_p=0.0, seed=0, part_dw=None, part_db=None,
-                  part_dbias=None):
-    """X: the forward's LN input, bf16 or f32 (the f32 hidden stream: mmu_layernorm_bwd_f32)."""
+                  part_dbias=None, row_step=None, row_offset=0):
+    """X: the forward's LN input, bf16 or f32 (the f32 hidden stream: mmu_layernorm_bwd_f32).
+    row_step (not None: mmu_layernorm_bwd_f32_rows, f32 X only) / row_offset: row r of dXdrop
+    draws the dropout decisions of row row_offset + r * row_step."""
     x32 = X.dtype == torch.float32
+    stepped = row_step is not None
+    if stepped and not x32:
+        raise N.NativeError("layernorm_bwd: row_step / row_offset need an f32 X")
     rows, H = _ln_rows("layernorm_bwd", X, torch.float32 if x32 else torch.bfloat16,
                        same=(("dY", dY), ("dX", dX), ("dXdrop", dXdrop)), vecs=(("mean", mean), ("rstd", rstd)),
                        parts=(("part_dw", part_dw), ("part_db", part_db), ("part_dbias", part_dbias)))
     _ln_params("layernorm_bwd", rows, H, 0, 0, w=w)
     _dev_check(dY, X, mean, rstd, w, dX, dXdrop, part_dw, part_db, part_dbias)
+    if stepped:
+        N.call("mmu_layernorm_bwd_f32_rows", _ptr(dY), _ptr(X), _ptr(mean), _ptr(rstd), _ptr(w), _ptr(dX),
+               _ptr(dXdrop), float(drop_p), int(seed), _ptr(part_dw), _ptr(part_db), _ptr(part_dbias), rows, H,
+               LN_ROWS_PER_PART, int(row_step), int(row_offset), _stream(X))
+        return
     N.call("mmu_layernorm_bwd_f32" if x32 else "mmu_layernorm_bwd", _ptr(dY), _ptr(X), _ptr(mean), _ptr(rstd),
            _ptr(w), _ptr(dX), _ptr(dXdrop), float(drop_p), int(seed), _ptr(part_dw), _ptr(part_db), _ptr(part_dbias),
            rows, H, LN_ROWS_PER_PART, _stream(X))
