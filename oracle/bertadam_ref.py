@@ -14,6 +14,13 @@ this follows its published algorithm:
         step += 1
     sched = warmup_linear(x, w): x/w if x < w else max((x-1)/(w-1), 0)
 
+Data parallelism folds its 1/world into the step (``grad_scale``): the optimizer's gradient is
+g * grad_scale, so the norm is taken of g * grad_scale and the update multiplies g by
+grad_scale * clip coefficient (csrc/optim.hip adam_coef_kernel).
+
+The arithmetic runs in the tensors' own dtype: float32 lists give the float32 rounding model of
+the fused kernel, float64 lists its high-precision reference (tests/bertadam_harness.py).
+
 Parity: "unpinned" beyond that formula (no executable BertAdam exists offline).
 """
 import torch
@@ -32,16 +39,20 @@ def schedule_factor(step, warmup, t_total):
 
 
 def bertadam_step(params, grads, ms, vs, steps, lr, wds, warmup, t_total,
-                  b1=0.9, b2=0.999, eps=1e-6, max_grad_norm=1.0):
-    """In-place fp32 update of lists of tensors; ``steps`` is a list of ints (returned +1)."""
+                  b1=0.9, b2=0.999, eps=1e-6, max_grad_norm=1.0, grad_scale=1.0):
+    """In-place update of lists of tensors (fp32, or fp64 for a reference); ``steps`` is a list of
+    ints (returned +1)."""
     new_steps = []
     for p, g, m, v, st, wd in zip(params, grads, ms, vs, steps, wds):
         g = g.clone()
+        coef = grad_scale
         if max_grad_norm > 0:
-            n = g.double().norm().item()
-            coef = max_grad_norm / (n + 1e-6)
-            if coef < 1.0:
-                g.mul_(coef)
+            n = g.double().norm().item() * grad_scale
+            clip = max_grad_norm / (n + 1e-6)
+            if clip < 1.0:
+                coef = clip * grad_scale
+        if coef != 1.0:
+            g.mul_(coef)
         m.mul_(b1).add_(g, alpha=1 - b1)
         v.mul_(b2).addcmul_(g, g, value=1 - b2)
         upd = m / (v.sqrt() + eps)

@@ -1,5 +1,6 @@
 """Guarded device buffers for the kernel edge sweeps (test_attention_edges_gpu.py,
-test_layernorm_edges_gpu.py, test_embed_edges_gpu.py): every tensor a kernel sees is a view of a
+test_layernorm_edges_gpu.py, test_embed_edges_gpu.py, test_batchnorm_edges_gpu.py,
+test_bertadam_edges_gpu.py): every tensor a kernel sees is a view of a
 larger allocation.  Input guards hold NaN, so a read through them poisons the result; outputs are
 pre-filled with a canary, and afterwards everything outside the view must be bit-identical to it.
   out_buf / check_written: NaN-filled contiguous outputs and their check after a launch;
@@ -29,7 +30,7 @@ class Guarded:
         self.canary = self.alloc.clone()
 
     def _bits(self, t):
-        return t.view({2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
+        return t.view({1: torch.int8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
 
     def refill(self):
         self.alloc.copy_(self.canary)
@@ -46,9 +47,9 @@ class Guarded:
 
 
 def guarded_input(dev, data, ld=None):
-    """data (CPU) copied into a NaN-surrounded device buffer -> the view"""
+    """data (CPU) copied into a NaN-surrounded device buffer (integer data: 85-surrounded) -> the view"""
     if ld is None:
-        g = Guarded(dev, data.dtype, float("nan"), data.numel())
+        g = Guarded(dev, data.dtype, float("nan") if data.is_floating_point() else 85, data.numel())
         g.view.copy_(data.reshape(-1))
         return g.view.view(data.shape)
     g = Guarded(dev, data.dtype, float("nan"), data.shape[0], data.shape[1], ld)
@@ -56,11 +57,18 @@ def guarded_input(dev, data, ld=None):
     return g.view
 
 
-def out_buf(dev, dtype, *shape):
+def inout_buf(dev, data, fill=NAN):
+    """data (CPU or device) copied into a guarded buffer a kernel updates in place -> (Guarded, view)"""
+    g = Guarded(dev, data.dtype, fill, data.numel())
+    g.view.copy_(data.reshape(-1))
+    return g, g.view.view(data.shape)
+
+
+def out_buf(dev, dtype, *shape, fill=NAN):
     n = 1
     for s in shape:
         n *= s
-    g = Guarded(dev, dtype, NAN, n)
+    g = Guarded(dev, dtype, fill, n)
     return g, g.view.view(*shape)
 
 
