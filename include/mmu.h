@@ -49,6 +49,21 @@ const char* mmu_last_error(void);
  * (No reference counterpart: the reference draws torch's RNG per dropout call.) */
 int mmu_set_seed_offset(const uint64_t* dev_counter);
 
+/* Deterministic mode (new symbols, ABI stays 4).  Off: every entry launches what it always did.
+ * On: no entry reaches a float atomicAdd; the column folds (mmu_colsum_reduce[_multi] and every
+ * entry that folds through them), the column sums of mmu_gemm / mmu_colsum_bf16, mmu_embed_bwd
+ * and mmu_ece_bins take fixed-order reductions whose result depends on the inputs and the shape
+ * alone.  Host state, read when a launch is chosen: a captured graph keeps the mode it was
+ * captured under.  Initial value: 1 if the environment holds MMU_DETERMINISTIC=1 at the first call
+ * into the library, else 0.  Both work without a GPU.
+ *   mmu_gemm with a plain colsum (not the *_STATS / *_BNB tables) always takes the partial-row
+ *     path, whatever MMU_GEMM_CS_PART says; batch > 1 with a colsum is refused (mmu_last_error);
+ *   mmu_colsum_bf16 over more than 1024 rows needs its scratch table;
+ *   mmu_embed_bwd needs the larger workspace mmu_embed_bwd_ws_floats() reports while the mode is
+ *     on (16-B aligned). */
+int mmu_set_deterministic(int on); /* -> the previous value */
+int mmu_get_deterministic(void);
+
 /* ------------------------------------------------------------------ GEMM
  * C[m,n] (op)= sum_k A(m,k) * B(n,k), batched over `batch` with element strides.
  *   A(m,k) = A[m*lda + k] if a_kmajor else A[k*lda + m]      (bf16)
@@ -317,8 +332,13 @@ int mmu_embed_fwd(const int64_t* ids, const int64_t* seg, const int64_t* txt_mas
  * pre-LN sums, LN backward, then scatters: word rows by atomics, position / type
  * / [CLS] / [SEP] by batch reduction, image rows to dproj f32 [B, n_img, H].
  * ws: f32 workspace of at least mmu_embed_bwd_ws_floats(B, T, n_img) floats (ABI 3; ABI 2 took
- * B*S*H + 2*ceil(B*S/64)*H, which is larger for every B > 1). */
+ * B*S*H + 2*ceil(B*S/64)*H, which is larger for every B > 1).
+ * Deterministic mode: the size query returns the larger workspace of that mode (the text rows'
+ * f32 gradients [B*T, H], the position partials [ceil(B/16), S, H], the segmented sum's carry
+ * rows, the sort's pairs and counters) while the mode is on; the word rows are then summed per
+ * id over the tokens in stable sorted order, in chunks of mmu_embed_bwd_det_chunk() tokens. */
 int64_t mmu_embed_bwd_ws_floats(int64_t B, int64_t T, int64_t n_img);
+int64_t mmu_embed_bwd_det_chunk(void);
 int mmu_embed_bwd(const void* dX, const int64_t* ids, const int64_t* seg,
                   const float* proj, const float* word, const float* pos, const float* type,
                   const float* ln_w, const float* mean, const float* rstd,

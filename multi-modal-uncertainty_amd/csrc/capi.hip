@@ -3,6 +3,7 @@
 // stream, and reports failures through a thread-local message (mmu_last_error).
 #include <stdarg.h>
 #include <stdio.h>
+#include <atomic>
 #include <map>
 #include <tuple>
 #include <mutex>
@@ -18,6 +19,27 @@ static thread_local std::string g_err;
 
 namespace mmu {
 const uint64_t* g_seed_off = nullptr;
+
+// deterministic mode (mmu_set_deterministic): host state, read when a launch is chosen.  -1: not
+// read yet; the first reader takes MMU_DETERMINISTIC=1 from the environment.
+static std::atomic<int> g_det{-1};
+bool deterministic() {
+  int v = g_det.load(std::memory_order_relaxed);
+  if (v < 0) {
+    const char* e = getenv("MMU_DETERMINISTIC");
+    int want = (e && atoi(e) == 1) ? 1 : 0;
+    if (!g_det.compare_exchange_strong(v, want)) want = v;
+    v = want;
+  }
+  return v != 0;
+}
+}
+
+int mmu_get_deterministic(void) { return mmu::deterministic() ? 1 : 0; }
+int mmu_set_deterministic(int on) {
+  const int prev = mmu::deterministic() ? 1 : 0;
+  mmu::g_det.store(on ? 1 : 0);
+  return prev;
 }
 
 int mmu_set_seed_offset(const uint64_t* dev_counter) {
@@ -288,13 +310,20 @@ static int gemm_impl(const void* A, int64_t lda, int a_kmajor, const void* B, in
   // column sums as partial rows (no float atomics: 50 us of the 0.74 ms dZ product at batch 256,
   // 180 us on the wide tile; profiles/r6_gemm_colsum_ab.txt), folded by one colsum_reduce launch.
   // Rows of 16 NJ per wave block: 128 on the 256 x 256 tile, 64 on the others.  MMU_GEMM_CS_PART=0: atomics.
+  // Deterministic mode: always the partial rows, whatever MMU_GEMM_CS_PART says; a plain colsum that
+  // cannot take them (batch > 1, no scratch) is refused below instead of reaching the atomics.
+  const bool det = deterministic();
   const char* csp_env = getenv("MMU_GEMM_CS_PART");
-  const bool cs_rows_ok = p.colsum && batch == 1 && p.splitk == 1 && kind != MMU_EPI_STORE_STATS &&
-                          kind != MMU_EPI_STORE_BNB && kind != MMU_EPI_ADD_RES_BNB && (!csp_env || atoi(csp_env) != 0);
+  const bool cs_plain = p.colsum && kind != MMU_EPI_STORE_STATS && kind != MMU_EPI_STORE_BNB &&
+                        kind != MMU_EPI_ADD_RES_BNB;
+  const bool cs_rows_ok = cs_plain && batch == 1 && p.splitk == 1 && (det || !csp_env || atoi(csp_env) != 0);
   const int cs_rows_main = (big && !wide) ? 128 : 64;
   const int64_t cs_parts_main = (m_main + cs_rows_main - 1) / cs_rows_main;
   const int64_t cs_parts = cs_parts_main + (tail_rows + 63) / 64;
   float* cs_part = cs_rows_ok ? tail_workspace(cs_parts * N, s, 1) : nullptr;
+  if (det && cs_plain && !cs_part)
+    return fail("mmu_gemm: deterministic mode: colsum with batch=%ld splitk=%d has no partial-row path%s",
+                batch, p.splitk, cs_rows_ok ? " (no scratch: table too large, or first use under stream capture)" : "");
   if (cs_part) {
     p.cs_part = cs_part;
     p.cs_m0 = 0;
@@ -388,6 +417,9 @@ int mmu_colsum_reduce_multi(int n, const float* const* partial, const int64_t* p
 int mmu_colsum_bf16(const void* X, int64_t M, int64_t N, int64_t ldx, float* partial, float* out, int accumulate,
                     mmu_stream_t stream) {
   if (!X || !out || M <= 0 || N <= 0 || N % 8 || ldx % 8) return fail("mmu_colsum_bf16: bad args");
+  if (deterministic() && !partial && M > colsum_bf16_rows_max())
+    return fail("mmu_colsum_bf16: deterministic mode: M=%ld spans more than one row block and needs the scratch table",
+                M);
   colsum_bf16_launch((const bf16*)X, M, N, ldx, partial, out, accumulate, (hipStream_t)stream);
   return check_launch("mmu_colsum_bf16");
 }
@@ -614,8 +646,11 @@ int mmu_embed_fwd(const int64_t* ids, const int64_t* seg, const int64_t* txt_mas
 }
 
 int64_t mmu_embed_bwd_ws_floats(int64_t B, int64_t T, int64_t n_img) {
-  return 4 * embed_bwd_blocks(B, n_img + 2 + T) * 768;
+  const int64_t base = 4 * embed_bwd_blocks(B, n_img + 2 + T) * 768;
+  return deterministic() ? base + embed_bwd_det_ws_floats(B, T, n_img) : base;
 }
+
+int64_t mmu_embed_bwd_det_chunk(void) { return embed_bwd_det_chunk(); }
 
 int mmu_embed_bwd(const void* dX, const int64_t* ids, const int64_t* seg, const float* proj, const float* word,
                   const float* pos, const float* type, const float* ln_w, const float* mean, const float* rstd,
@@ -632,6 +667,10 @@ int mmu_embed_bwd(const void* dX, const int64_t* ids, const int64_t* seg, const 
   q.ln_w = ln_w; q.mean = mean; q.rstd = rstd; q.cls_id = cls_id; q.sep_id = sep_id; q.B = B; q.T = T;
   q.n_img = n_img; q.H = H; q.drop_txt = drop_txt; q.drop_img = drop_img; q.seed = seed; q.seed_off = g_seed_off; q.d_word = d_word; q.d_pos = d_pos; q.d_type = d_type; q.d_ln_w = d_ln_w;
   q.d_ln_b = d_ln_b; q.d_proj = d_proj; q.ws = ws;
+  if (deterministic()) {
+    if ((uintptr_t)ws & 15) return fail("mmu_embed_bwd: deterministic mode: ws must be 16-B aligned");
+    if (B * T >= (1ll << 31)) return fail("mmu_embed_bwd: deterministic mode: B*T must be < 2^31");
+  }
   embed_bwd_launch(q, (hipStream_t)stream);
   return check_launch("mmu_embed_bwd");
 }

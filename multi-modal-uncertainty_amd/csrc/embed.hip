@@ -109,6 +109,10 @@ void embed_fwd_launch(const EmbedParams& p, hipStream_t s) {
 // colsum_reduce.  (Round 6: the batch sums used to go through an f32 [B, S, H] copy of the row
 // gradients and a second kernel walking it column-wise: 0.69 ms at B = 256 for 0.4 GB.)
 constexpr int EBW_B = 16;  // samples per block
+// DET (deterministic mode): no atomics.  A text row's dx goes to the scratch dxs [B * T, 768] and
+// the wave's position sum to postab [ceil(B / EBW_B), S, 768], both behind the partial rows in q.ws
+// (16 B per lane, whole lines); embed_bwd_launch sums them in a fixed order afterwards.
+template <bool DET>
 __global__ __launch_bounds__(256) void embed_bwd_rows_kernel(EmbedBwdParams q, EmbedParams p) {
   __shared__ float red[4][4][768];                            // aw, ab, type-0, type-1 per wave
   __shared__ __attribute__((aligned(16))) float xch[4][768];  // per wave: a text row's dx, re-read lane-contiguous
@@ -117,6 +121,8 @@ __global__ __launch_bounds__(256) void embed_bwd_rows_kernel(EmbedBwdParams q, E
   const int64_t nblk = (int64_t)gridDim.x * gridDim.y;
   const int64_t blk = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
   float* part = q.ws;
+  float* dxs = q.ws + 4 * nblk * H;
+  float* postab = dxs + q.B * q.T * H;
   const int64_t s = (int64_t)blockIdx.x * 4 + wv;
   const int64_t b0 = (int64_t)blockIdx.y * EBW_B;
   const bool live = s < S;
@@ -168,12 +174,15 @@ __global__ __launch_bounds__(256) void embed_bwd_rows_kernel(EmbedBwdParams q, E
         if (seg1) t1[i][k] += dx[k];
       }
       if (text) {
-        *(float4*)(&xch[wv][c]) = make_float4(dx[0], dx[1], dx[2], dx[3]);
+        if (DET)
+          *(float4*)(dxs + (b * q.T + (s - q.n_img - 2)) * H + c) = make_float4(dx[0], dx[1], dx[2], dx[3]);
+        else
+          *(float4*)(&xch[wv][c]) = make_float4(dx[0], dx[1], dx[2], dx[3]);
       } else if (img) {
         *(float4*)(q.d_proj + (b * q.n_img + (s - 1)) * H + c) = make_float4(dx[0], dx[1], dx[2], dx[3]);
       }
     }
-    if (text) {  // word-row scatter: every atomic instruction adds 256 contiguous bytes (lane l ->
+    if (text && !DET) {  // word-row scatter: every atomic instruction adds 256 contiguous bytes (lane l ->
                  // column 64 j + l); 16-B-strided lanes ran the memory-side atomics at a fraction
                  // of their rate.  The row sits in this wave's own LDS slice: in-order LDS, no barrier.
       __builtin_amdgcn_wave_barrier();
@@ -182,7 +191,13 @@ __global__ __launch_bounds__(256) void embed_bwd_rows_kernel(EmbedBwdParams q, E
       __builtin_amdgcn_wave_barrier();
     }
   }
-  if (live) {  // this position's sum over the block's samples: position row, [CLS] / [SEP] word rows
+  if (live && DET) {  // this position's sum over the block's samples: its row of the block's table slab
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+      *(float4*)(postab + ((int64_t)blockIdx.y * S + s) * H + 256 * i + 4 * l) =
+          make_float4(tot[i][0], tot[i][1], tot[i][2], tot[i][3]);
+  }
+  if (live && !DET) {  // this position's sum over the block's samples: position row, [CLS] / [SEP] word rows
                // (through the wave's LDS slice: lane-contiguous 256-B atomic instructions)
     const int64_t posr = text ? s - q.n_img - 2 : s;
     float* wr = s == 0 ? q.d_word + q.cls_id * H : (s == q.n_img + 1 ? q.d_word + q.sep_id * H : nullptr);
@@ -217,6 +232,284 @@ __global__ __launch_bounds__(256) void embed_bwd_rows_kernel(EmbedBwdParams q, E
 
 int64_t embed_bwd_blocks(int64_t B, int64_t S) { return ((S + 3) / 4) * ((B + EBW_B - 1) / EBW_B); }
 
+// ---------------------------------------------------------------- backward, deterministic mode
+// d_word = a segmented sum over the text tokens sorted by id.  The pairs (id, flat row b T + t) are
+// sorted by a stable LSD radix sort of the 32 key bits (the entry is not told the vocabulary), 8
+// bits a pass: per tile of SORT_TILE keys one wave counts the digits (LDS integer counters), one
+// block scans the [tiles][256] counts digit-major, and one wave per tile places its keys in index
+// order (the rank among the wave's equal digits from ballots).  Stable, so the rows of one id
+// ascend.  Nothing is allocated: pairs and counters lie in the workspace.
+constexpr int SORT_TILE = 1024;
+constexpr int EBW_DET_CHUNK = 64;  // tokens of the sorted sequence per wave of the segmented sum
+
+template <bool FIRST>
+__global__ __launch_bounds__(64) void sort_hist_kernel(const int64_t* __restrict__ ids,
+                                                       const uint32_t* __restrict__ keys, int64_t n, int shift,
+                                                       uint32_t* __restrict__ counts, int64_t ntile) {
+  __shared__ uint32_t h[256];
+  const int l = threadIdx.x;
+  for (int d = l; d < 256; d += 64) h[d] = 0;
+  __syncthreads();
+  for (int st = 0; st < SORT_TILE / 64; ++st) {
+    const int64_t i = (int64_t)blockIdx.x * SORT_TILE + st * 64 + l;
+    if (i < n) {
+      const uint32_t k = FIRST ? (uint32_t)ids[i] : keys[i];
+      atomicAdd(&h[(k >> shift) & 255], 1u);
+    }
+  }
+  __syncthreads();
+  for (int d = l; d < 256; d += 64) counts[(int64_t)blockIdx.x * 256 + d] = h[d];
+}
+
+// exclusive scan of counts[tile][digit] in (digit, tile) order, in place: thread d walks its digit's
+// column over the tiles (coalesced across the block), then adds the total of the smaller digits
+__global__ __launch_bounds__(256) void sort_scan_kernel(uint32_t* __restrict__ counts, int64_t ntile) {
+  __shared__ uint32_t tot[256];
+  const int d = threadIdx.x;
+  uint32_t run = 0;
+#pragma unroll 8
+  for (int64_t t = 0; t < ntile; ++t) run += counts[t * 256 + d];
+  tot[d] = run;
+  __syncthreads();
+  uint32_t base = 0;
+  for (int e = 0; e < d; ++e) base += tot[e];
+#pragma unroll 8
+  for (int64_t t = 0; t < ntile; ++t) {
+    const uint32_t c = counts[t * 256 + d];
+    counts[t * 256 + d] = base;
+    base += c;
+  }
+}
+
+template <bool FIRST>
+__global__ __launch_bounds__(64) void sort_scatter_kernel(const int64_t* __restrict__ ids,
+                                                          const uint32_t* __restrict__ keys,
+                                                          const uint32_t* __restrict__ vals, uint32_t* __restrict__ keys_out,
+                                                          uint32_t* __restrict__ vals_out, int64_t n, int shift,
+                                                          const uint32_t* __restrict__ counts, int64_t ntile) {
+  __shared__ uint32_t base[256];
+  const int l = threadIdx.x;
+  for (int d = l; d < 256; d += 64) base[d] = counts[(int64_t)blockIdx.x * 256 + d];
+  __syncthreads();
+  for (int st = 0; st < SORT_TILE / 64; ++st) {
+    const int64_t i = (int64_t)blockIdx.x * SORT_TILE + st * 64 + l;
+    const bool valid = i < n;
+    const uint32_t k = valid ? (FIRST ? (uint32_t)ids[i] : keys[i]) : 0u;
+    const uint32_t v = valid ? (FIRST ? (uint32_t)i : vals[i]) : 0u;
+    const uint32_t d = (k >> shift) & 255;
+    uint64_t peers = __ballot(valid);  // the valid lanes holding this lane's digit
+#pragma unroll
+    for (int bit = 0; bit < 8; ++bit) {
+      const bool on = (d >> bit) & 1;
+      const uint64_t m = __ballot(on);
+      peers &= on ? m : ~m;
+    }
+    const int rank = __popcll(peers & ((1ull << l) - 1));
+    if (valid) {
+      const uint32_t dst = base[d] + rank;
+      keys_out[dst] = k;
+      vals_out[dst] = v;
+    }
+    __syncthreads();
+    if (valid && rank == 0) base[d] += __popcll(peers);
+    __syncthreads();
+  }
+}
+
+// 4 consecutive floats of a gradient row: 16-B accesses where the caller's buffer allows them (the
+// flat gradient store packs its tensors without padding), else four 4-B ones
+static __device__ __forceinline__ float4 ld4(const float* p) {
+  return ((uintptr_t)p & 15) == 0 ? *(const float4*)p : make_float4(p[0], p[1], p[2], p[3]);
+}
+static __device__ __forceinline__ void st4(float* p, float4 v) {
+  if (((uintptr_t)p & 15) == 0) {
+    *(float4*)p = v;
+  } else {
+    p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w;
+  }
+}
+static __device__ __forceinline__ void row_rmw(float* __restrict__ dst, const float (&acc)[3][4], int l) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    float* d = dst + 256 * i + 4 * l;
+    float4 o = ld4(d);
+    o.x += acc[i][0]; o.y += acc[i][1]; o.z += acc[i][2]; o.w += acc[i][3];
+    st4(d, o);
+  }
+}
+static __device__ __forceinline__ void row_store(float* __restrict__ dst, const float (&acc)[3][4], int l) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+    *(float4*)(dst + 256 * i + 4 * l) = make_float4(acc[i][0], acc[i][1], acc[i][2], acc[i][3]);
+}
+
+// First level of the segmented sum: one wave per chunk of EBW_DET_CHUNK sorted tokens walks them
+// in order and sums each run of equal ids in registers.  A run that lies inside the chunk has this
+// wave as its only writer: d_word[id] += sum.  A run that goes on from the previous chunk leaves
+// its sum in carry row 0 of the chunk, one that begins here and goes on into the next chunk in
+// carry row 1; embed_det_carry_kernel folds those.
+__global__ __launch_bounds__(64) void embed_det_chunk_kernel(const uint32_t* __restrict__ sk,
+                                                             const uint32_t* __restrict__ sv, int64_t n,
+                                                             const float* __restrict__ dxs, float* __restrict__ carry,
+                                                             float* __restrict__ d_word) {
+  const int l = threadIdx.x;
+  const int64_t c = blockIdx.x, c0 = c * EBW_DET_CHUNK;
+  const int cnt = (int)(n - c0 < EBW_DET_CHUNK ? n - c0 : EBW_DET_CHUNK);
+  const uint32_t my_k = l < cnt ? sk[c0 + l] : 0u, my_v = l < cnt ? sv[c0 + l] : 0u;
+  const bool has_left = c0 > 0, has_right = c0 + cnt < n;
+  const uint32_t left_k = has_left ? sk[c0 - 1] : 0u, right_k = has_right ? sk[c0 + cnt] : 0u;
+  float acc[3][4];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) acc[i][k] = 0.f;
+  uint32_t cur = __shfl(my_k, 0, 64);
+  bool first = true;
+  for (int i = 0; i <= cnt; ++i) {
+    const uint32_t k = __shfl(my_k, i < cnt ? i : 0, 64);
+    if (i == cnt || k != cur) {  // the run of `cur` ends before token i
+      const bool left_open = first && has_left && left_k == cur;
+      const bool right_open = i == cnt && has_right && right_k == cur;
+      if (left_open) row_store(carry + (2 * c) * 768, acc, l);
+      else if (right_open) row_store(carry + (2 * c + 1) * 768, acc, l);
+      else row_rmw(d_word + (int64_t)cur * 768, acc, l);
+      if (i == cnt) break;
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) acc[a][b] = 0.f;
+      cur = k;
+      first = false;
+    }
+    add_row(acc, dxs + (int64_t)__shfl(my_v, i, 64) * 768, l);
+  }
+}
+
+// Second level: the run that begins in chunk c and goes on past its end has one writer per 256
+// columns here, which adds carry row 1 of c and then carry row 0 of every later chunk the run
+// reaches, in chunk order, and d_word[id] += that sum.  The run's end is found by bisection of the
+// sorted keys.
+__global__ __launch_bounds__(64) void embed_det_carry_kernel(const uint32_t* __restrict__ sk, int64_t n,
+                                                             const float* __restrict__ carry,
+                                                             float* __restrict__ d_word) {
+  const int64_t c = blockIdx.x, c0 = c * EBW_DET_CHUNK, c1 = c0 + EBW_DET_CHUNK;
+  if (c1 >= n) return;
+  const uint32_t id = sk[c1 - 1];
+  if (sk[c1] != id) return;                                // nothing goes on past this chunk
+  if (sk[c0] == id && c0 > 0 && sk[c0 - 1] == id) return;  // the run began in an earlier chunk
+  int64_t lo = c1, hi = n;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (sk[mid] <= id) lo = mid + 1;
+    else hi = mid;
+  }
+  const int64_t clast = (lo - 1) / EBW_DET_CHUNK;
+  const int col = blockIdx.y * 256 + 4 * threadIdx.x;
+  float4 a = *(const float4*)(carry + (2 * c + 1) * 768 + col);
+#pragma unroll 8
+  for (int64_t cc = c + 1; cc <= clast; ++cc) {
+    const float4 v = *(const float4*)(carry + (2 * cc) * 768 + col);
+    a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+  }
+  float* d = d_word + (int64_t)id * 768 + col;
+  float4 o = ld4(d);
+  o.x += a.x; o.y += a.y; o.z += a.z; o.w += a.w;
+  st4(d, o);
+}
+
+// Position rows and the [CLS] / [SEP] word rows from postab [nby, S, 768], one writer each, the
+// nby block rows folded in block order.  Block r < R: d_pos[r] += (the image-segment position r)
+// then (the text position r).  Block R, after every token run of the launches before it:
+// d_word[cls] += position 0's sum, then d_word[sep] += position n_img + 1's (one thread per
+// column does both, so cls == sep stays ordered).
+__global__ __launch_bounds__(64) void embed_det_pos_kernel(const float* __restrict__ postab, int64_t nby, int64_t S,
+                                                           int64_t T, int64_t n_img, int64_t R, int64_t cls_id,
+                                                           int64_t sep_id, float* __restrict__ d_pos,
+                                                           float* __restrict__ d_word) {
+  const int col = blockIdx.y * 256 + 4 * threadIdx.x;
+  const int64_t r = blockIdx.x;
+  auto fold = [&](float* dst, int64_t s) {
+    float4 a = ld4(dst + col);
+    for (int64_t by = 0; by < nby; ++by) {
+      const float4 v = *(const float4*)(postab + (by * S + s) * 768 + col);
+      a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+    }
+    st4(dst + col, a);
+  };
+  if (r < R) {
+    if (r <= n_img + 1) fold(d_pos + r * 768, r);
+    if (r < T) fold(d_pos + r * 768, n_img + 2 + r);
+  } else {
+    fold(d_word + cls_id * 768, 0);
+    fold(d_word + sep_id * 768, n_img + 1);
+  }
+}
+
+namespace {
+struct DetLayout {  // offsets in floats behind the [4, nblk, 768] partial rows; every section 16-B aligned
+  int64_t n, nby, S, nch, ntile, n4;
+  int64_t dxs, postab, carry, keys[2], vals[2], counts, total;
+};
+DetLayout det_layout(int64_t B, int64_t T, int64_t n_img) {
+  DetLayout d{};
+  d.n = B * T;
+  d.nby = (B + EBW_B - 1) / EBW_B;
+  d.S = n_img + 2 + T;
+  d.nch = (d.n + EBW_DET_CHUNK - 1) / EBW_DET_CHUNK;
+  d.ntile = (d.n + SORT_TILE - 1) / SORT_TILE;
+  d.n4 = (d.n + 3) / 4 * 4;
+  int64_t o = 0;
+  d.dxs = o; o += d.n * 768;
+  d.postab = o; o += d.nby * d.S * 768;
+  d.carry = o; o += d.nch * 2 * 768;
+  for (int i = 0; i < 2; ++i) { d.keys[i] = o; o += d.n4; }
+  for (int i = 0; i < 2; ++i) { d.vals[i] = o; o += d.n4; }
+  d.counts = o; o += 256 * d.ntile;
+  d.total = o;
+  return d;
+}
+}  // namespace
+
+int64_t embed_bwd_det_ws_floats(int64_t B, int64_t T, int64_t n_img) { return det_layout(B, T, n_img).total; }
+int64_t embed_bwd_det_chunk() { return EBW_DET_CHUNK; }
+
+static void embed_bwd_det_launch(const EmbedBwdParams& q, const EmbedParams& p, int64_t nblk, hipStream_t s) {
+  const DetLayout d = det_layout(q.B, q.T, q.n_img);
+  float* base = q.ws + 4 * nblk * 768;  // (dxs and postab: the rows kernel derives the same addresses)
+  hipLaunchKernelGGL(embed_bwd_rows_kernel<true>, dim3((unsigned)((p.Lout + 3) / 4), (unsigned)d.nby), dim3(256), 0, s,
+                     q, p);
+  if (d.n > 0) {
+    uint32_t* keys[2] = {(uint32_t*)(base + d.keys[0]), (uint32_t*)(base + d.keys[1])};
+    uint32_t* vals[2] = {(uint32_t*)(base + d.vals[0]), (uint32_t*)(base + d.vals[1])};
+    uint32_t* counts = (uint32_t*)(base + d.counts);
+    const dim3 tiles((unsigned)d.ntile);
+    for (int pass = 0; pass < 4; ++pass) {  // pass 0 reads the ids; the sorted pairs end in keys[1] / vals[1]
+      const int in = (pass + 1) & 1, out = pass & 1, shift = 8 * pass;
+      if (pass == 0)
+        hipLaunchKernelGGL(sort_hist_kernel<true>, tiles, dim3(64), 0, s, q.ids, (const uint32_t*)nullptr, d.n, shift,
+                           counts, d.ntile);
+      else
+        hipLaunchKernelGGL(sort_hist_kernel<false>, tiles, dim3(64), 0, s, (const int64_t*)nullptr, keys[in], d.n,
+                           shift, counts, d.ntile);
+      hipLaunchKernelGGL(sort_scan_kernel, dim3(1), dim3(256), 0, s, counts, d.ntile);
+      if (pass == 0)
+        hipLaunchKernelGGL(sort_scatter_kernel<true>, tiles, dim3(64), 0, s, q.ids, (const uint32_t*)nullptr,
+                           (const uint32_t*)nullptr, keys[out], vals[out], d.n, shift, counts, d.ntile);
+      else
+        hipLaunchKernelGGL(sort_scatter_kernel<false>, tiles, dim3(64), 0, s, (const int64_t*)nullptr, keys[in],
+                           vals[in], keys[out], vals[out], d.n, shift, counts, d.ntile);
+    }
+    hipLaunchKernelGGL(embed_det_chunk_kernel, dim3((unsigned)d.nch), dim3(64), 0, s, keys[1], vals[1], d.n,
+                       base + d.dxs, base + d.carry, q.d_word);
+    if (d.nch > 1)
+      hipLaunchKernelGGL(embed_det_carry_kernel, dim3((unsigned)d.nch, 3), dim3(64), 0, s, keys[1], d.n,
+                         base + d.carry, q.d_word);
+  }
+  const int64_t R = q.n_img + 2 > q.T ? q.n_img + 2 : q.T;
+  hipLaunchKernelGGL(embed_det_pos_kernel, dim3((unsigned)(R + 1), 3), dim3(64), 0, s, base + d.postab, d.nby, d.S,
+                     q.T, q.n_img, R, q.cls_id, q.sep_id, q.d_pos, q.d_word);
+}
+
 void embed_bwd_launch(const EmbedBwdParams& q, hipStream_t s) {
   EmbedParams p{};
   p.ids = q.ids; p.seg = q.seg; p.txt_mask = nullptr; p.idx = nullptr;
@@ -224,8 +517,11 @@ void embed_bwd_launch(const EmbedBwdParams& q, hipStream_t s) {
   p.cls_id = q.cls_id; p.sep_id = q.sep_id; p.V = 1; p.B = q.B; p.T = q.T; p.n_img = q.n_img;
   p.Lout = q.n_img + 2 + q.T; p.H = 768;
   const int64_t nblk = embed_bwd_blocks(q.B, p.Lout);
-  hipLaunchKernelGGL(embed_bwd_rows_kernel, dim3((unsigned)((p.Lout + 3) / 4), (unsigned)((q.B + EBW_B - 1) / EBW_B)),
-                     dim3(256), 0, s, q, p);
+  if (deterministic())
+    embed_bwd_det_launch(q, p, nblk, s);
+  else
+    hipLaunchKernelGGL(embed_bwd_rows_kernel<false>, dim3((unsigned)((p.Lout + 3) / 4), (unsigned)((q.B + EBW_B - 1) / EBW_B)),
+                       dim3(256), 0, s, q, p);
   const float* part = q.ws;
   ColsumJobs jobs{};
   float* outs[4] = {q.d_ln_w, q.d_ln_b, q.d_type, q.d_type + 768};

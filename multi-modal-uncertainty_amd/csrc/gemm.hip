@@ -1187,7 +1187,66 @@ __global__ __launch_bounds__(256) void colsum_reduce_kernel(const float* __restr
   atomicAdd(out + n, s);
 }
 
+// Deterministic mode: the same folds with one writer per column and no atomics, one launch, no
+// memset.  A block of 1024 threads = 8 lanes x CF_G row groups over 8 VEC columns (VEC = 4: 16 B
+// per lane, one 128-B line per row): group g sums rows g, g + CF_G, ... in order, the group sums go
+// through LDS, and thread j folds column j's CF_G sums in group order and stores
+// (acc ? out : 0) + sum.  The order is a function of (parts, N) alone.  VEC = 1 (N % 4 or a
+// pointer off 16 B) is the same walk with 4-B accesses.
+constexpr int CF_G = 128;
+template <int VEC>
+static __device__ __forceinline__ void colsum_fold_body(const float* __restrict__ part, int64_t parts, int64_t N,
+                                                        float* __restrict__ out, int acc) {
+  __shared__ float red[CF_G][8 * VEC];
+  const int cx = threadIdx.x & 7, g = threadIdx.x >> 3;
+  const int64_t n0 = (int64_t)blockIdx.x * (8 * VEC), n = n0 + cx * VEC;
+  float a[VEC];
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) a[e] = 0.f;
+  if (n < N) {
+#pragma unroll 8
+    for (int64_t r = g; r < parts; r += CF_G) {
+      if constexpr (VEC == 4) {
+        const float4 v = *(const float4*)(part + r * N + n);
+        a[0] += v.x; a[1] += v.y; a[2] += v.z; a[3] += v.w;
+      } else {
+        a[0] += part[r * N + n];
+      }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) red[g][cx * VEC + e] = a[e];
+  __syncthreads();
+  const int j = threadIdx.x;
+  if (j < 8 * VEC && n0 + j < N) {
+    float t = 0.f;
+#pragma unroll 16
+    for (int q = 0; q < CF_G; ++q) t += red[q][j];
+    out[n0 + j] = (acc ? out[n0 + j] : 0.f) + t;
+  }
+}
+template <int VEC>
+__global__ __launch_bounds__(1024) void colsum_fold_det_kernel(const float* __restrict__ part, int64_t parts,
+                                                               int64_t N, float* __restrict__ out, int acc) {
+  colsum_fold_body<VEC>(part, parts, N, out, acc);
+}
+template <int VEC>
+__global__ __launch_bounds__(1024) void colsum_fold_multi_det_kernel(const ColsumJobs jobs, int64_t N, int acc) {
+  const int z = blockIdx.y;
+  colsum_fold_body<VEC>(jobs.part[z], jobs.parts[z], N, jobs.out[z], acc);
+}
+static bool fold_vec4(const float* part, int64_t N) { return N % 4 == 0 && ((uintptr_t)part & 15) == 0; }
+
 void colsum_reduce_launch(const float* part, int64_t parts, int64_t N, float* out, int acc, hipStream_t s) {
+  if (deterministic()) {
+    if (fold_vec4(part, N))
+      hipLaunchKernelGGL(colsum_fold_det_kernel<4>, dim3((unsigned)((N + 31) / 32)), dim3(1024), 0, s, part, parts, N,
+                         out, acc);
+    else
+      hipLaunchKernelGGL(colsum_fold_det_kernel<1>, dim3((unsigned)((N + 7) / 8)), dim3(1024), 0, s, part, parts, N,
+                         out, acc);
+    return;
+  }
   if (!acc) (void)hipMemsetAsync(out, 0, sizeof(float) * N, s);
   hipLaunchKernelGGL(colsum_reduce_kernel,
                      dim3((unsigned)((N + 255) / 256), (unsigned)((parts + COLSUM_ROWS - 1) / COLSUM_ROWS)),
@@ -1212,6 +1271,17 @@ __global__ __launch_bounds__(256) void colsum_reduce_multi_kernel(const ColsumJo
 }
 
 void colsum_reduce_multi_launch(const ColsumJobs& jobs, int n, int64_t N, int acc, hipStream_t s) {
+  if (deterministic()) {
+    bool v4 = true;
+    for (int z = 0; z < n; ++z) v4 = v4 && fold_vec4(jobs.part[z], N);
+    if (v4)
+      hipLaunchKernelGGL(colsum_fold_multi_det_kernel<4>, dim3((unsigned)((N + 31) / 32), (unsigned)n), dim3(1024), 0,
+                         s, jobs, N, acc);
+    else
+      hipLaunchKernelGGL(colsum_fold_multi_det_kernel<1>, dim3((unsigned)((N + 7) / 8), (unsigned)n), dim3(1024), 0, s,
+                         jobs, N, acc);
+    return;
+  }
   int64_t most = 0;
   for (int z = 0; z < n; ++z) {
     if (!acc) (void)hipMemsetAsync(jobs.out[z], 0, sizeof(float) * N, s);
@@ -1229,9 +1299,12 @@ void colsum_reduce_multi_launch(const ColsumJobs& jobs, int n, int64_t N, int ac
 // block (short blocks would pile hundreds of same-address atomics into the L2 queue).
 constexpr int COLSUM_BF16_ROWS = 1024;
 constexpr int COLSUM_BF16_MIN_ROWS = 64;
+// DET (deterministic mode, a single row block and no scratch table): the block is the only writer
+// of its columns and stores (acc ? out : 0) + sum instead of the atomics.
+template <bool DET>
 __global__ __launch_bounds__(256) void colsum_bf16_kernel(const bf16* __restrict__ X, int64_t M, int64_t N,
                                                           int64_t ld, int64_t rpb, float* __restrict__ part,
-                                                          float* __restrict__ out) {
+                                                          float* __restrict__ out, int acc) {
   const int64_t r0 = (int64_t)blockIdx.y * rpb;
   const int64_t r1 = r0 + rpb < M ? r0 + rpb : M;
   const int64_t c = ((int64_t)blockIdx.x * 64 + (threadIdx.x & 63)) * 8;
@@ -1269,6 +1342,9 @@ __global__ __launch_bounds__(256) void colsum_bf16_kernel(const bf16* __restrict
       float4* d = (float4*)(part + (int64_t)blockIdx.y * N + c);
       d[0] = make_float4(t[0], t[1], t[2], t[3]);
       d[1] = make_float4(t[4], t[5], t[6], t[7]);
+    } else if (DET) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) out[c + e] = (acc ? out[c + e] : 0.f) + t[e];
     } else {
 #pragma unroll
       for (int e = 0; e < 8; ++e) atomicAdd(out + c + e, t[e]);
@@ -1287,15 +1363,21 @@ void colsum_bf16_launch(const bf16* X, int64_t M, int64_t N, int64_t ld, float* 
   }
   const int64_t gy = (M + rpb - 1) / rpb;
   if (part && gy > 1) {
-    hipLaunchKernelGGL(colsum_bf16_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, s, X, M, N, ld, rpb, part,
-                       (float*)nullptr);
-    colsum_reduce_launch(part, gy, N, out, acc, s);
+    hipLaunchKernelGGL(colsum_bf16_kernel<false>, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, s, X, M, N, ld, rpb,
+                       part, (float*)nullptr, 0);
+    colsum_reduce_launch(part, gy, N, out, acc, s);  // (the fixed-order fold in deterministic mode)
+    return;
+  }
+  if (deterministic()) {  // one row block (mmu_colsum_bf16 refuses more without a table): no atomics, no memset
+    hipLaunchKernelGGL(colsum_bf16_kernel<true>, dim3((unsigned)gx, 1), dim3(256), 0, s, X, M, N, ld, M,
+                       (float*)nullptr, out, acc);
     return;
   }
   if (!acc) (void)hipMemsetAsync(out, 0, sizeof(float) * N, s);
-  hipLaunchKernelGGL(colsum_bf16_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, s, X, M, N, ld, rpb,
-                     (float*)nullptr, out);
+  hipLaunchKernelGGL(colsum_bf16_kernel<false>, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, s, X, M, N, ld, rpb,
+                     (float*)nullptr, out, 0);
 }
+int64_t colsum_bf16_rows_max() { return COLSUM_BF16_ROWS; }
 
 // ------------------------------------------------------------------ batched transpose
 // one 64 x 64 tile per workgroup through LDS (row pitch 65 elements: conflict-free column

@@ -10,6 +10,9 @@ namespace mmu {
 
 // mmu_set_seed_offset's device counter (capi.hip), copied into every dropout launch
 extern const uint64_t* g_seed_off;
+// deterministic mode (mmu_set_deterministic / MMU_DETERMINISTIC=1): every launcher that would
+// reach a float atomicAdd reads it and takes a fixed-order reduction instead
+bool deterministic();
 
 struct GemmParams {
   const bf16* A;
@@ -92,6 +95,7 @@ struct ColsumJobs {  // (passed by value: graph-capturable)
 void colsum_reduce_multi_launch(const ColsumJobs& jobs, int n, int64_t N, int acc, hipStream_t s);
 void colsum_bf16_launch(const bf16* X, int64_t M, int64_t N, int64_t ld, float* part, float* out, int acc,
                         hipStream_t s);
+int64_t colsum_bf16_rows_max();  // rows one block of colsum_bf16 takes without a scratch table
 
 struct AttnParams {
   const bf16* qkv;
@@ -171,6 +175,10 @@ struct EmbedBwdParams {
 };
 void embed_bwd_launch(const EmbedBwdParams& p, hipStream_t s);
 int64_t embed_bwd_blocks(int64_t B, int64_t S);
+// deterministic mode: the floats embed_bwd_launch takes behind the [4, nblk, 768] partial rows,
+// and the segmented sum's chunk (tokens per wave)
+int64_t embed_bwd_det_ws_floats(int64_t B, int64_t T, int64_t n_img);
+int64_t embed_bwd_det_chunk();
 void image_normalize_launch(const uint8_t* in, int64_t n, const float* mean, const float* stdv, void* out,
                             bool out_bf16, hipStream_t s);
 void maxpool3s2_fwd_launch(const bf16* x, int64_t B, int H, int W, int C, int OH, int OW, bf16* y, uint8_t* am,

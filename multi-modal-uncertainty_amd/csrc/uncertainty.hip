@@ -82,7 +82,39 @@ void uncertainty_launch(const float* logits, const int64_t* y, int64_t S, int64_
   hipLaunchKernelGGL(uncertainty_kernel, dim3((unsigned)S), dim3(128), 0, s, logits, y, R, C, p_bar, nll, conf, correct);
 }
 
+// Deterministic mode: one wave per bin, no atomics and no memset.  Lane l walks samples l, l + 64,
+// ... in index order and keeps the bin's count / conf / correct sums of its own samples; the 64 lane
+// sums are folded by the fixed butterfly of wave_sum, and lane 0 stores the bin's three figures.
+__global__ __launch_bounds__(64) void ece_bins_det_kernel(const float* __restrict__ conf,
+                                                          const float* __restrict__ correct, int64_t S, int n_bins,
+                                                          float* __restrict__ out) {
+  const int bin = blockIdx.x;
+  float cnt = 0.f, sc = 0.f, sk = 0.f;
+  for (int64_t i = threadIdx.x; i < S; i += 64) {
+    const float c = conf[i];
+    int b = (int)ceilf(c * n_bins) - 1;
+    b = b < 0 ? 0 : (b >= n_bins ? n_bins - 1 : b);
+    if (b == bin) {
+      cnt += 1.f;
+      sc += c;
+      sk += correct[i];
+    }
+  }
+  cnt = wave_sum(cnt);
+  sc = wave_sum(sc);
+  sk = wave_sum(sk);
+  if (threadIdx.x == 0) {
+    out[3 * bin] = cnt;
+    out[3 * bin + 1] = sc;
+    out[3 * bin + 2] = sk;
+  }
+}
+
 void ece_bins_launch(const float* conf, const float* correct, int64_t S, int64_t n_bins, float* out, hipStream_t s) {
+  if (deterministic()) {
+    hipLaunchKernelGGL(ece_bins_det_kernel, dim3((unsigned)n_bins), dim3(64), 0, s, conf, correct, S, (int)n_bins, out);
+    return;
+  }
   (void)hipMemsetAsync(out, 0, sizeof(float) * 3 * n_bins, s);
   hipLaunchKernelGGL(ece_bins_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, s, conf, correct, S,
                      (int)n_bins, out);

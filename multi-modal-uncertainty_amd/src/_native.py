@@ -35,6 +35,9 @@ SIGNATURES = {
     "mmu_embed_bwd_ws_floats": (c_i64, [c_i64, c_i64, c_i64]),
     "mmu_last_error": (ctypes.c_char_p, []),
     "mmu_set_seed_offset": (c_i32, [c_vp]),
+    "mmu_set_deterministic": (c_i32, [c_i32]),
+    "mmu_get_deterministic": (c_i32, []),
+    "mmu_embed_bwd_det_chunk": (c_i64, []),
     "mmu_gemm": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_i64, c_i64, c_i64,
                          c_i64, c_i64, c_i64, c_i64, ctypes.POINTER(Epilogue), c_vp]),
     "mmu_gemm_rows": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_vp, c_i64, c_i32, c_i64, c_i64, c_i64,

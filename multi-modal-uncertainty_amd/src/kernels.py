@@ -20,6 +20,38 @@ def bn_stats_table(rows, C, device):
     return torch.empty(nparts * C * 2, dtype=torch.float32, device=device), nparts
 
 
+def set_deterministic(on):
+    """Deterministic mode of the library (mmu_set_deterministic): with it on, no kernel sums through
+    float atomics, so equal inputs give equal bits.  Host state read when a launch is chosen; a
+    captured graph keeps the mode it was captured under.  -> the previous value"""
+    return bool(N.load().mmu_set_deterministic(int(bool(on))))
+
+
+def is_deterministic():
+    return bool(N.load().mmu_get_deterministic())
+
+
+class deterministic:
+    """``with kernels.deterministic():`` turns the mode on (or off: ``deterministic(False)``) and
+    restores the previous value on exit, after an exception too"""
+
+    def __init__(self, on=True):
+        self.on = on
+
+    def __enter__(self):
+        self.prev = set_deterministic(self.on)
+        return self
+
+    def __exit__(self, *exc):
+        set_deterministic(self.prev)
+        return False
+
+
+def embed_bwd_det_chunk():
+    """tokens per wave of the deterministic embedding backward's segmented sum"""
+    return int(N.load().mmu_embed_bwd_det_chunk())
+
+
 def _dev_check(*ts):
     for t in ts:
         if t is not None and not t.is_cuda:

@@ -11,10 +11,13 @@ Additions (all optional):
                      loss / metric sums combined over the ranks in Model_.eval_loop),
                      rank 0 writes history / checkpoints.
   --synthetic with --framework flava: seeded FLAVA embeddings (197 image + <= 77 text tokens)
+  --deterministic    bitwise-repeatable steps (kernels.set_deterministic + MIOpen's deterministic
+                     algorithms); recorded in <save_path>/run_meta.json; gin: train.deterministic=1
 --framework vilt is refused: the reference's setup_vilt needs the remote dandelin/vilt-b32-mlm
 weights and ViltProcessor; the ViLT training step itself is src.vilt.ViltTrainHIP.
 """
 import argparse
+import json
 import logging
 import os
 import sys
@@ -67,12 +70,30 @@ FLAGS = [
     # build additions
     ("--gin_file", dict(nargs="*", default=[])), ("--gin_param", dict(nargs="*", default=[])),
     ("--synthetic", dict(type=int, default=0, help="N synthetic samples instead of $DATA_DIR/<dataset>")),
+    ("--deterministic", dict(action="store_true", help="bitwise-repeatable training steps: the HIP kernels sum in "
+                                                       "a fixed order (no float atomics) and MIOpen picks "
+                                                       "deterministic conv algorithms (DESIGN.md, Determinism)")),
 ]
 
 
 def get_args(parser):
     for flag, kw in FLAGS:
         parser.add_argument(flag, **kw)
+
+
+def apply_deterministic(args):
+    """--deterministic: the library's deterministic mode and MIOpen's deterministic conv algorithms"""
+    if getattr(args, "deterministic", False):
+        from src import kernels
+        kernels.set_deterministic(True)
+        torch.backends.cudnn.deterministic = True
+
+
+def run_meta(args):
+    """what <save_path>/run_meta.json records of a run"""
+    return {"framework": args.framework, "dataset": args.dataset, "model_type": args.model_type, "seed": args.seed,
+            "batch_size": args.batch_size, "synthetic": int(args.synthetic),
+            "deterministic": bool(args.deterministic)}
 
 
 def add_conditional_args(args):
@@ -233,6 +254,7 @@ def main(argv=None):
         logger.warning("gin bindings not mapped to train.py flags: %s", sorted(unused))
     args = add_conditional_args(args)
     set_seed(args.seed)
+    apply_deterministic(args)
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     if world > 1:
         import torch.distributed as dist
@@ -257,6 +279,9 @@ def main(argv=None):
         args, model, optimizer, scheduler = setup_mmbt(args)
     mmbt = args.framework == "mmbt"
     os.makedirs(args.save_path, exist_ok=True)
+    if rank == 0:
+        with open(os.path.join(args.save_path, "run_meta.json"), "w") as f:
+            json.dump(run_meta(args), f)
     history_csv_path = os.path.join(args.save_path, "history.csv")
     if args.resume:
         ck = torch.load(os.path.join(args.save_path, "model_last_epoch.pt"), map_location="cpu", weights_only=True)
