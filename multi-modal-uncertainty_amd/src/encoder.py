@@ -18,6 +18,9 @@ and LN inputs stay f32, as in the reference's fp32 layer:
 with the stream rounded to bf16 at each of the 48 LN / residual points of 12 layers the
 logits drift by up to 1.6 % of their scale (CPU emulation of the rounding points,
 DESIGN.md §4), with it f32 by 0.5 %.
+Everything behind the attention is row-wise and written once (_rows_forward / _rows_backward):
+layer_forward / layer_backward run it on all M rows, the [CLS]-only last layer
+(last_layer_forward / last_layer_backward) on the B [CLS] rows.
 Backward mirrors it (the gradient stream is bf16); weight gradients are written straight into the flat f32
 gradient buffer (src/params.py) and skipped when the layer is frozen
 (src/framework.py:284-285 toggles requires_grad).
@@ -70,6 +73,31 @@ class LayerWeights:
         return self.anchor.requires_grad
 
 
+def _rows_forward(lw, O, R, res_ln, rows, p_hid, seeds, save, row_step=None):
+    """The row-wise chain behind the attention, on ``rows`` rows: Wo + dropout + residual, LN1,
+    W1 + GELU, W2 + dropout + residual -> (S1, mean1, rstd1, A, Z, Hh, S2).  The dense layer's
+    B L rows (row_step None: mmu_gemm), or the last layer's B [CLS] rows with row_step = L, whose
+    row b then draws the hidden dropout of the dense layer's row b L."""
+    dev = O.device
+    f32 = torch.float32
+    S1 = torch.empty(rows, HID, dtype=f32, device=dev)
+    K.gemm(O, HID, True, lw.wo16, HID, True, S1, HID, rows, HID, HID,
+           epi=K.epilogue(K.EPI_BIAS_DROP_RES, bias=lw.bo, residual=R, drop_p=p_hid, seed=seeds[1], res_ln=res_ln),
+           row_step=row_step)
+    A = torch.empty(rows, HID, dtype=bf16, device=dev)
+    mean1 = torch.empty(rows, dtype=f32, device=dev)
+    rstd1 = torch.empty(rows, dtype=f32, device=dev)
+    K.layernorm_fwd_f32(S1, lw.ln1w, lw.ln1b, A, None, mean1, rstd1)
+    Z = torch.empty(rows, FFN, dtype=bf16, device=dev) if save else None  # gelu'(A W1^T + b1), for the backward
+    Hh = torch.empty(rows, FFN, dtype=bf16, device=dev)
+    K.gemm(A, HID, True, lw.w116, HID, True, Hh, FFN, rows, FFN, HID, epi=K.epilogue(K.EPI_BIAS_GELU, bias=lw.b1, aux=Z))
+    S2 = torch.empty(rows, HID, dtype=f32, device=dev)
+    K.gemm(Hh, FFN, True, lw.w216, FFN, True, S2, HID, rows, HID, FFN,
+           epi=K.epilogue(K.EPI_BIAS_DROP_RES, bias=lw.b2, residual=S1, drop_p=p_hid, seed=seeds[2],
+                          res_ln=(mean1, rstd1, lw.ln1w, lw.ln1b)), row_step=row_step)
+    return S1, mean1, rstd1, A, Z, Hh, S2
+
+
 def layer_forward(lw, X, R, keymask, B, L, p_attn, p_hid, seeds, save, res_ln=None, out32=False):
     """X bf16 [M, 768] and its f32 residual -> (Y bf16, S2, mean2, rstd2, saved, Y32).
 
@@ -87,20 +115,7 @@ def layer_forward(lw, X, R, keymask, B, L, p_attn, p_hid, seeds, save, res_ln=No
     lse = torch.empty(B * HEADS, L, dtype=torch.float32, device=dev)
     dmask = K.dropmask_empty(B, L, HEADS, dev) if (save and p_attn > 0) else None
     K.attention_fwd(qkv, keymask, O, lse, B, L, HEADS, p_attn, seeds[0], dmask)
-    S1 = torch.empty(M, HID, dtype=f32, device=dev)
-    K.gemm(O, HID, True, lw.wo16, HID, True, S1, HID, M, HID, HID,
-           epi=K.epilogue(K.EPI_BIAS_DROP_RES, bias=lw.bo, residual=R, drop_p=p_hid, seed=seeds[1], res_ln=res_ln))
-    A = torch.empty(M, HID, dtype=bf16, device=dev)
-    mean1 = torch.empty(M, dtype=f32, device=dev)
-    rstd1 = torch.empty(M, dtype=f32, device=dev)
-    K.layernorm_fwd_f32(S1, lw.ln1w, lw.ln1b, A, None, mean1, rstd1)
-    Z = torch.empty(M, FFN, dtype=bf16, device=dev) if save else None  # gelu'(A W1^T + b1), for the backward
-    Hh = torch.empty(M, FFN, dtype=bf16, device=dev)
-    K.gemm(A, HID, True, lw.w116, HID, True, Hh, FFN, M, FFN, HID, epi=K.epilogue(K.EPI_BIAS_GELU, bias=lw.b1, aux=Z))
-    S2 = torch.empty(M, HID, dtype=f32, device=dev)
-    K.gemm(Hh, FFN, True, lw.w216, FFN, True, S2, HID, M, HID, FFN,
-           epi=K.epilogue(K.EPI_BIAS_DROP_RES, bias=lw.b2, residual=S1, drop_p=p_hid, seed=seeds[2],
-                          res_ln=(mean1, rstd1, lw.ln1w, lw.ln1b)))
+    S1, mean1, rstd1, A, Z, Hh, S2 = _rows_forward(lw, O, R, res_ln, M, p_hid, seeds, save)
     Y = torch.empty(M, HID, dtype=bf16, device=dev)
     Y32 = torch.empty(M, HID, dtype=f32, device=dev) if out32 is True else None
     mean2 = torch.empty(M, dtype=f32, device=dev)
@@ -149,21 +164,7 @@ def last_layer_forward(lw, X, R, keymask, B, L, p_attn, p_hid, seeds, save, res_
     Rc = _cls_rows(R, B, L)
     if res_ln is not None:
         res_ln = (_cls_rows(res_ln[0], B, L), _cls_rows(res_ln[1], B, L), res_ln[2], res_ln[3])
-    S1 = torch.empty(B, HID, dtype=f32, device=dev)
-    K.gemm(Oc, HID, True, lw.wo16, HID, True, S1, HID, B, HID, HID,
-           epi=K.epilogue(K.EPI_BIAS_DROP_RES, bias=lw.bo, residual=Rc, drop_p=p_hid, seed=seeds[1], res_ln=res_ln),
-           row_step=L)
-    A = torch.empty(B, HID, dtype=bf16, device=dev)
-    mean1 = torch.empty(B, dtype=f32, device=dev)
-    rstd1 = torch.empty(B, dtype=f32, device=dev)
-    K.layernorm_fwd_f32(S1, lw.ln1w, lw.ln1b, A, None, mean1, rstd1)
-    Z = torch.empty(B, FFN, dtype=bf16, device=dev) if save else None
-    Hh = torch.empty(B, FFN, dtype=bf16, device=dev)
-    K.gemm(A, HID, True, lw.w116, HID, True, Hh, FFN, B, FFN, HID, epi=K.epilogue(K.EPI_BIAS_GELU, bias=lw.b1, aux=Z))
-    S2 = torch.empty(B, HID, dtype=f32, device=dev)
-    K.gemm(Hh, FFN, True, lw.w216, FFN, True, S2, HID, B, HID, FFN,
-           epi=K.epilogue(K.EPI_BIAS_DROP_RES, bias=lw.b2, residual=S1, drop_p=p_hid, seed=seeds[2],
-                          res_ln=(mean1, rstd1, lw.ln1w, lw.ln1b)), row_step=L)
+    S1, mean1, rstd1, A, Z, Hh, S2 = _rows_forward(lw, Oc, Rc, res_ln, B, p_hid, seeds, save, row_step=L)
     Y32 = torch.empty(B, HID, dtype=f32, device=dev)
     mean2 = torch.empty(B, dtype=f32, device=dev)
     rstd2 = torch.empty(B, dtype=f32, device=dev)
@@ -183,38 +184,9 @@ def last_layer_backward(lw, saved, dY32, keymask, B, L, p_attn, p_hid, seeds, wg
     X, Xc, qkv, Oc, lse0, kw0, S1, mean1, rstd1, A, Z, Hh, S2, mean2, rstd2 = saved
     M = B * L
     dev = dY32.device
-    P = K.ln_parts(B)
     side = _Side(dev, wgrad)
-    pw = pb = pbias = pw1 = pb1 = pbias1 = None
-    if wgrad:
-        pw, pb, pbias, pw1, pb1, pbias1 = (torch.empty(P, HID, dtype=torch.float32, device=dev) for _ in range(6))
-    acc = K.epilogue(K.EPI_STORE, accumulate=True)
-    dY = dY32.to(bf16).contiguous()
-    # ---- output LayerNorm + dropout + W2
-    dS2 = torch.empty(B, HID, dtype=bf16, device=dev)
-    dY2 = torch.empty(B, HID, dtype=bf16, device=dev)
-    K.layernorm_bwd(dY, S2, mean2, rstd2, lw.ln2w, dS2, dY2, p_hid, seeds[2], pw, pb, pbias, row_step=L)
-    if wgrad:
-        def w2():
-            K.colsum_reduce_multi([(pw, lw.g_ln2w), (pb, lw.g_ln2b), (pbias, lw.g_b2)], accumulate=True)
-            K.gemm(dY2, HID, False, Hh, FFN, False, lw.g_w2, FFN, HID, FFN, B, epi=acc)
-        side.run(w2, pw, pb, pbias, dY2, Hh)
-    dZ = torch.empty(B, FFN, dtype=bf16, device=dev)
-    K.gemm(dY2, HID, True, lw.w2t16, HID, True, dZ, FFN, B, FFN, HID,
-           epi=K.epilogue(K.EPI_DGELU, aux=Z, colsum=lw.g_b1 if wgrad else None))
-    if wgrad:
-        side.run(lambda: K.gemm(dZ, FFN, False, A, HID, False, lw.g_w1, HID, FFN, HID, B, epi=acc), dZ, A)
-    dA = torch.empty(B, HID, dtype=bf16, device=dev)
-    K.gemm(dZ, FFN, True, lw.w1t16, FFN, True, dA, HID, B, HID, FFN, epi=K.epilogue(K.EPI_ADD_RES, residual=dS2))
-    # ---- attention-output LayerNorm + dropout + Wo
-    dS1 = torch.empty(B, HID, dtype=bf16, device=dev)
-    dAo = torch.empty(B, HID, dtype=bf16, device=dev)
-    K.layernorm_bwd(dA, S1, mean1, rstd1, lw.ln1w, dS1, dAo, p_hid, seeds[1], pw1, pb1, pbias1, row_step=L)
-    if wgrad:
-        def wo():
-            K.colsum_reduce_multi([(pw1, lw.g_ln1w), (pb1, lw.g_ln1b), (pbias1, lw.g_bo)], accumulate=True)
-            K.gemm(dAo, HID, False, Oc, HID, False, lw.g_wo, HID, HID, HID, B, epi=acc)
-        side.run(wo, pw1, pb1, pbias1, dAo, Oc)
+    dS1, dAo = _rows_backward(lw, side, dY32.to(bf16).contiguous(), S2, mean2, rstd2, Hh, Z, A, S1, mean1, rstd1, Oc,
+                              B, p_hid, seeds, wgrad, row_step=L)
     # ---- attention (query row 0) + fused QKV.  The kernel addresses dO / O / lse / the keep
     # words as the dense ones do: dense-shaped buffers with row 0 of each sequence filled in
     dO = torch.empty(M, HID, dtype=bf16, device=dev)
@@ -232,6 +204,8 @@ def last_layer_backward(lw, saved, dY32, keymask, B, L, p_attn, p_hid, seeds, wg
     K.attention_row0_bwd(qkv, keymask, O, dO, lse, dqkv, B, L, HEADS, p_attn, dmask, dbs)
     dqkv_c = _cls_rows(dqkv, B, L)  # [B, 2304]: the full dQ | dK | dV rows of the [CLS] tokens
     if wgrad:
+        acc = K.epilogue(K.EPI_STORE, accumulate=True)
+
         def wqkv():
             K.colsum_reduce_multi([(dbs[0], lw.g_bqkv[:HID]), (dbs[1], lw.g_bqkv[HID:2 * HID]),
                                    (dbs[2], lw.g_bqkv[2 * HID:])], accumulate=True)
@@ -296,19 +270,13 @@ def _defer_budget(dev):
     return torch.cuda.get_device_properties(dev).total_memory // 4
 
 
-# INTERLEAVE (MMU_WGRAD_INTERLEAVE=1): at the end of the encoder's data-gradient chain the deferred
-# work is not issued at once but item by item from the trunk's BatchNorm backwards
-# (K.side_pump, called by src/resnet.py), the rest when the backward ends.  A HIP graph replays
-# its nodes in capture order, so the all-at-once flush runs the ~200 weight-gradient kernels
-# before the first trunk kernel even at batch 32, where they would fit beside the trunk's
-# short BatchNorm / conv kernels (profiles/r6_wgrad_interleave_ab.txt).
-# MMU_WGRAD_INTERLEAVE=2: the first trunk BatchNorm backward issues ALL of it, behind everything the
-# main stream has enqueued by then (the embedding and image-projection backward then run without the
-# side stream's weight-gradient GEMMs holding every CU)
-# (default 2: -0.37 ms at batch 256, neutral at 32, profiles/r6_wgrad_flush_late_ab.txt; 0 = round 5)
-INTERLEAVE = os.environ.get("MMU_WGRAD_INTERLEAVE", "2") != "0"
-INTERLEAVE_ALL = os.environ.get("MMU_WGRAD_INTERLEAVE", "2") == "2"
-_pending = {}  # per device: flushed items not yet issued (INTERLEAVE)
+# The work flushed at the end of the encoder's data-gradient chain is not issued there but by the
+# first trunk BatchNorm backward (K.side_pump, called by src/resnet.py), behind everything the
+# main stream has enqueued by then: the embedding and image-projection backward then run without
+# the side stream's weight-gradient GEMMs holding every CU (-0.37 ms at batch 256, neutral at 32,
+# profiles/r6_wgrad_flush_late_ab.txt; issuing it item by item from every BatchNorm backward
+# lost, profiles/r6_wgrad_interleave_ab.txt)
+_pending = {}  # per device: flushed items not yet issued
 
 
 def _issue(dev, items):
@@ -324,11 +292,11 @@ def _issue(dev, items):
             _block_extra.append((e0, _mark()))
 
 
-def _flush_deferred(dev, interleave=False):
+def _flush_deferred(dev, late=False):
     """Issue the deferred weight-gradient work (and the DP hooks after it) on the side stream,
     behind everything the main stream has enqueued so far -- the whole encoder dX chain -- so
     it runs beside what follows (embedding backward, the ResNet trunk's backward); with
-    `interleave` it is handed to pump_deferred instead."""
+    `late` it is handed to pump_deferred instead."""
     items = _deferred.pop(dev, None)
     _deferred_bytes.pop(dev, None)
     if not items:
@@ -336,23 +304,19 @@ def _flush_deferred(dev, interleave=False):
     main = torch.cuda.current_stream(dev)
     side = K.side_stream(dev)
     side.wait_stream(main)
-    if interleave:
+    if late:
         _pending.setdefault(dev, []).extend(items)
     else:
         _issue(dev, items)
     K.join_at_backward_end(main, side)
 
 
-def pump_deferred(dev, n=1):
-    """issue up to n of the flushed items (INTERLEAVE) on the side stream (INTERLEAVE_ALL: all of
-    them, after the main stream's work so far)"""
-    items = _pending.get(dev)
+def pump_deferred(dev):
+    """issue the flushed items on the side stream, after the main stream's work so far"""
+    items = _pending.pop(dev, None)
     if items:
-        if INTERLEAVE_ALL:
-            K.side_stream(dev).wait_stream(torch.cuda.current_stream(dev))
-            n = len(items)
-        _pending[dev] = items[n:]
-        _issue(dev, items[:n])
+        K.side_stream(dev).wait_stream(torch.cuda.current_stream(dev))
+        _issue(dev, items)
 
 
 K.set_side_pump(pump_deferred)
@@ -399,42 +363,53 @@ class _Side:
         return fn()
 
 
-def layer_backward(lw, saved, dY, keymask, B, L, p_attn, p_hid, seeds, wgrad):
-    X, qkv, O, lse, dmask, S1, mean1, rstd1, A, Z, Hh, S2, mean2, rstd2 = saved
-    M = B * L
+def _rows_backward(lw, side, dY, S2, mean2, rstd2, Hh, Z, A, S1, mean1, rstd1, O, rows, p_hid, seeds, wgrad,
+                   row_step=None):
+    """The backward of _rows_forward on ``rows`` rows (dY bf16: the gradient of LN2's output):
+    LN2', W2, gelu', W1, LN1' and the weight gradients of W2, W1, Wo (``O``: Wo's operand) with
+    their bias / LayerNorm column sums, handed to ``side`` -> (dS1, dAo), the gradients of the
+    residual stream at the attention output and of O Wo^T + bo."""
     dev = dY.device
-    P = K.ln_parts(M)
-    side = _Side(dev, wgrad)
+    P = K.ln_parts(rows)
     pw = pb = pbias = pw1 = pb1 = pbias1 = None
     if wgrad:  # two sets: the side stream reduces one while the main stream fills the other
         pw, pb, pbias, pw1, pb1, pbias1 = (torch.empty(P, HID, dtype=torch.float32, device=dev) for _ in range(6))
     acc = K.epilogue(K.EPI_STORE, accumulate=True)
     # ---- output LayerNorm + dropout + W2
-    dS2 = torch.empty(M, HID, dtype=bf16, device=dev)
-    dY2 = torch.empty(M, HID, dtype=bf16, device=dev)
-    K.layernorm_bwd(dY, S2, mean2, rstd2, lw.ln2w, dS2, dY2, p_hid, seeds[2], pw, pb, pbias)
+    dS2 = torch.empty(rows, HID, dtype=bf16, device=dev)
+    dY2 = torch.empty(rows, HID, dtype=bf16, device=dev)
+    K.layernorm_bwd(dY, S2, mean2, rstd2, lw.ln2w, dS2, dY2, p_hid, seeds[2], pw, pb, pbias, row_step=row_step)
     if wgrad:
         def w2():
             K.colsum_reduce_multi([(pw, lw.g_ln2w), (pb, lw.g_ln2b), (pbias, lw.g_b2)], accumulate=True)
-            K.gemm(dY2, HID, False, Hh, FFN, False, lw.g_w2, FFN, HID, FFN, M, epi=acc)
+            K.gemm(dY2, HID, False, Hh, FFN, False, lw.g_w2, FFN, HID, FFN, rows, epi=acc)
         side.run(w2, pw, pb, pbias, dY2, Hh)
-    dZ = torch.empty(M, FFN, dtype=bf16, device=dev)
+    dZ = torch.empty(rows, FFN, dtype=bf16, device=dev)
     # dgelu epilogue also accumulates the intermediate-bias gradient (column sums of dZ) in place
-    K.gemm(dY2, HID, True, lw.w2t16, HID, True, dZ, FFN, M, FFN, HID,
+    K.gemm(dY2, HID, True, lw.w2t16, HID, True, dZ, FFN, rows, FFN, HID,
            epi=K.epilogue(K.EPI_DGELU, aux=Z, colsum=lw.g_b1 if wgrad else None))
     if wgrad:
-        side.run(lambda: K.gemm(dZ, FFN, False, A, HID, False, lw.g_w1, HID, FFN, HID, M, epi=acc), dZ, A)
-    dA = torch.empty(M, HID, dtype=bf16, device=dev)
-    K.gemm(dZ, FFN, True, lw.w1t16, FFN, True, dA, HID, M, HID, FFN, epi=K.epilogue(K.EPI_ADD_RES, residual=dS2))
+        side.run(lambda: K.gemm(dZ, FFN, False, A, HID, False, lw.g_w1, HID, FFN, HID, rows, epi=acc), dZ, A)
+    dA = torch.empty(rows, HID, dtype=bf16, device=dev)
+    K.gemm(dZ, FFN, True, lw.w1t16, FFN, True, dA, HID, rows, HID, FFN, epi=K.epilogue(K.EPI_ADD_RES, residual=dS2))
     # ---- attention-output LayerNorm + dropout + Wo
-    dS1 = torch.empty(M, HID, dtype=bf16, device=dev)
-    dAo = torch.empty(M, HID, dtype=bf16, device=dev)
-    K.layernorm_bwd(dA, S1, mean1, rstd1, lw.ln1w, dS1, dAo, p_hid, seeds[1], pw1, pb1, pbias1)
+    dS1 = torch.empty(rows, HID, dtype=bf16, device=dev)
+    dAo = torch.empty(rows, HID, dtype=bf16, device=dev)
+    K.layernorm_bwd(dA, S1, mean1, rstd1, lw.ln1w, dS1, dAo, p_hid, seeds[1], pw1, pb1, pbias1, row_step=row_step)
     if wgrad:
         def wo():
             K.colsum_reduce_multi([(pw1, lw.g_ln1w), (pb1, lw.g_ln1b), (pbias1, lw.g_bo)], accumulate=True)
-            K.gemm(dAo, HID, False, O, HID, False, lw.g_wo, HID, HID, HID, M, epi=acc)
+            K.gemm(dAo, HID, False, O, HID, False, lw.g_wo, HID, HID, HID, rows, epi=acc)
         side.run(wo, pw1, pb1, pbias1, dAo, O)
+    return dS1, dAo
+
+
+def layer_backward(lw, saved, dY, keymask, B, L, p_attn, p_hid, seeds, wgrad):
+    X, qkv, O, lse, dmask, S1, mean1, rstd1, A, Z, Hh, S2, mean2, rstd2 = saved
+    M = B * L
+    dev = dY.device
+    side = _Side(dev, wgrad)
+    dS1, dAo = _rows_backward(lw, side, dY, S2, mean2, rstd2, Hh, Z, A, S1, mean1, rstd1, O, M, p_hid, seeds, wgrad)
     dO = torch.empty(M, HID, dtype=bf16, device=dev)
     K.gemm(dAo, HID, True, lw.wot16, HID, True, dO, HID, M, HID, HID)
     # ---- attention + fused QKV
@@ -444,6 +419,8 @@ def layer_backward(lw, saved, dY, keymask, B, L, p_attn, p_hid, seeds, wgrad):
     dbp = K.attention_dbias_parts(B, L, HEADS, dev) if wgrad else None
     K.attention_bwd(qkv, keymask, O, dO, lse, delta, dqkv, B, L, HEADS, p_attn, seeds[0], dmask, dbp)
     if wgrad:
+        acc = K.epilogue(K.EPI_STORE, accumulate=True)
+
         def wqkv():
             K.attention_dbias_reduce(dbp, B, L, lw.g_bqkv, HEADS)
             K.gemm(dqkv, 3 * HID, False, X, HID, False, lw.g_wqkv, HID, 3 * HID, HID, M, epi=acc)
@@ -482,6 +459,18 @@ def _mark():
     e = torch.cuda.Event(enable_timing=True)
     e.record()
     return e
+
+
+def _after_backward(lw, side, wgrad, hook, flush):
+    """The end of a layer's autograd backward: the DP hook behind the layer's weight gradients
+    (deferred with them), and in layer 0's (``flush``: the encoder's last) the late flush."""
+    if wgrad and side.defer:
+        if hook is not None:  # the bucket all-reduce follows the layer's deferred work
+            _defer(side.dev, lambda: hook(lw), ())
+        if flush:
+            _flush_deferred(side.dev, late=True)
+    elif wgrad and hook is not None:
+        hook(lw)
 
 
 class BertLayerFunction(torch.autograd.Function):
@@ -527,15 +516,8 @@ class BertLayerFunction(torch.autograd.Function):
         if e0 is not None:
             _block_events.append((e0, _mark()))
         ctx.saved_bufs = None
-        if wgrad and side.defer:
-            if hook is not None:  # the bucket all-reduce follows the layer's deferred work
-                _defer(side.dev, lambda: hook(lw), ())
-            if flush:
-                _flush_deferred(side.dev, INTERLEAVE)
-        elif wgrad and hook is not None:
-            hook(lw)
+        _after_backward(lw, side, wgrad, hook, flush)
         return (dX,) + (None,) * 13
-
 
 
 class BertLastLayerFunction(torch.autograd.Function):
@@ -566,11 +548,5 @@ class BertLastLayerFunction(torch.autograd.Function):
         if e0 is not None:
             _block_events.append((e0, _mark()))
         ctx.saved_bufs = None
-        if wgrad and side.defer:
-            if hook is not None:  # the bucket all-reduce follows the layer's deferred work
-                _defer(side.dev, lambda: hook(lw), ())
-            if flush:
-                _flush_deferred(side.dev, INTERLEAVE)
-        elif wgrad and hook is not None:
-            hook(lw)
+        _after_backward(lw, side, wgrad, hook, flush)
         return (dX,) + (None,) * 12

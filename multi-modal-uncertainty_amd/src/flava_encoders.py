@@ -48,27 +48,42 @@ class _Layer:
         self.hid = self.wo.shape[0]
 
 
+def _layer_forward(X, keymask, lw, B, L, h=None, save=False):
+    """One pre-LN layer (the 12 x layer rows of the module docstring) on the f32 stream X
+    [B*L, H]; ``lw``: a _Layer, or any object with its fields.  -> (next stream, kept).
+    Without ``save`` (inference) both LayerNorms write the bf16 scratch ``h`` and ``kept`` is
+    None; with it, ``kept`` is what a backward needs, each in a buffer of its own: (h1, m1, r1,
+    qkv, O, lse, S, h2, m2, r2, G, Z) -- the LayerNorm outputs and statistics and Z = gelu'(.)."""
+    M, H = X.shape
+    F = lw.w1.shape[0]
+    dev, f32 = X.device, torch.float32
+    h1 = h2 = h
+    m1 = r1 = m2 = r2 = Z = None
+    if save:
+        h1, h2 = (torch.empty(M, H, dtype=bf16, device=dev) for _ in range(2))
+        m1, r1, m2, r2 = (torch.empty(M, dtype=f32, device=dev) for _ in range(4))
+        Z = torch.empty(M, F, dtype=bf16, device=dev)
+    K.layernorm_fwd_f32(X, lw.ln1[0], lw.ln1[1], h1, None, m1, r1, eps=lw.ln1[2])
+    qkv = torch.empty(M, 3 * H, dtype=bf16, device=dev)
+    K.gemm(h1, H, True, lw.wqkv, H, True, qkv, 3 * H, M, 3 * H, H, epi=K.epilogue(K.EPI_STORE, bias=lw.bqkv))
+    O = torch.empty(M, H, dtype=bf16, device=dev)
+    lse = torch.empty(B * lw.heads, L, dtype=f32, device=dev)
+    K.attention_fwd(qkv, keymask, O, lse, B, L, lw.heads, 0.0, 0, None)
+    S = torch.empty(M, H, dtype=f32, device=dev)
+    K.gemm(O, H, True, lw.wo, H, True, S, H, M, H, H, epi=K.epilogue(K.EPI_BIAS_DROP_RES, bias=lw.bo, residual=X))
+    K.layernorm_fwd_f32(S, lw.ln2[0], lw.ln2[1], h2, None, m2, r2, eps=lw.ln2[2])
+    G = torch.empty(M, F, dtype=bf16, device=dev)
+    K.gemm(h2, H, True, lw.w1, H, True, G, F, M, F, H, epi=K.epilogue(K.EPI_BIAS_GELU, bias=lw.b1, aux=Z))
+    Y = torch.empty(M, H, dtype=f32, device=dev)
+    K.gemm(G, F, True, lw.w2, F, True, Y, H, M, H, F, epi=K.epilogue(K.EPI_BIAS_DROP_RES, bias=lw.b2, residual=S))
+    return Y, ((h1, m1, r1, qkv, O, lse, S, h2, m2, r2, G, Z) if save else None)
+
+
 def _encoder_layers(X, keymask, layers, B, L):
     """f32 stream X [B*L, H] through the pre-LN FlavaLayers; returns the final f32 stream."""
-    M, H = X.shape
-    dev = X.device
-    h = torch.empty(M, H, dtype=bf16, device=dev)
+    h = torch.empty(X.shape, dtype=bf16, device=X.device)
     for lw in layers:
-        K.layernorm_fwd_f32(X, lw.ln1[0], lw.ln1[1], h, eps=lw.ln1[2])
-        qkv = torch.empty(M, 3 * H, dtype=bf16, device=dev)
-        K.gemm(h, H, True, lw.wqkv, H, True, qkv, 3 * H, M, 3 * H, H, epi=K.epilogue(K.EPI_STORE, bias=lw.bqkv))
-        O = torch.empty(M, H, dtype=bf16, device=dev)
-        lse = torch.empty(B * lw.heads, L, dtype=torch.float32, device=dev)
-        K.attention_fwd(qkv, keymask, O, lse, B, L, lw.heads, 0.0, 0, None)
-        S = torch.empty(M, H, dtype=torch.float32, device=dev)
-        K.gemm(O, H, True, lw.wo, H, True, S, H, M, H, H, epi=K.epilogue(K.EPI_BIAS_DROP_RES, bias=lw.bo, residual=X))
-        K.layernorm_fwd_f32(S, lw.ln2[0], lw.ln2[1], h, eps=lw.ln2[2])
-        F = lw.w1.shape[0]
-        g = torch.empty(M, F, dtype=bf16, device=dev)
-        K.gemm(h, H, True, lw.w1, H, True, g, F, M, F, H, epi=K.epilogue(K.EPI_BIAS_GELU, bias=lw.b1))
-        Xn = torch.empty(M, H, dtype=torch.float32, device=dev)
-        K.gemm(g, F, True, lw.w2, F, True, Xn, H, M, H, F, epi=K.epilogue(K.EPI_BIAS_DROP_RES, bias=lw.b2, residual=S))
-        X = Xn
+        X, _ = _layer_forward(X, keymask, lw, B, L, h)
     return X
 
 

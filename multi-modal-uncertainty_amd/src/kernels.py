@@ -175,15 +175,15 @@ _side_pump = None
 
 
 def set_side_pump(fn):
-    """src/encoder.py's pump_deferred: deferred side-stream work issued piecewise"""
+    """src/encoder.py's pump_deferred: issues the side-stream work it has flushed"""
     global _side_pump
     _side_pump = fn
 
 
-def side_pump(dev, n=1):
-    """issue up to n pieces of the encoder's flushed weight-gradient work (interleave mode)"""
+def side_pump(dev):
+    """issue the encoder's flushed weight-gradient work (the trunk's BatchNorm backwards call this)"""
     if _side_pump is not None:
-        _side_pump(dev, n)
+        _side_pump(dev)
 
 
 def side_stream_if_any(dev):

@@ -17,8 +17,6 @@ What runs where on the GPU:
   pooler + classifier   torch f32 (768x768, 768x101 on one row per sample)
 No CPU fallback: the encoder path raises on CPU tensors.
 """
-import os
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -27,9 +25,6 @@ from . import kernels as K
 from .encoder import LayerWeights, encoder_stack
 from .params import ParamStore
 from .resnet import StoreConv2d, resnet152_trunk
-
-# the encoder hands the pooler only the last layer's [CLS] rows (MMU_CLS_ONLY=0: all rows, round 5)
-CLS_ONLY = os.environ.get("MMU_CLS_ONLY", "1") != "0"
 
 BERT_CONFIGS = {
     # name: (layers, hidden, heads, intermediate, vocab, max_pos, type_vocab)
@@ -458,7 +453,7 @@ class MultimodalBertEncoder(nn.Module):
         need_grad = torch.is_grad_enabled() and (X.requires_grad or any(lw.trainable() for lw in self._lw))
         return encoder_stack(self._lw, X, X32, km, nb, L, p_attn, p_hid,
                              lambda i: (_mix(base, 3 * i), _mix(base, 3 * i + 1), _mix(base, 3 * i + 2)),
-                             need_grad, self._grad_ready_hook, cls_only=CLS_ONLY)
+                             need_grad, self._grad_ready_hook, cls_only=True)
 
     def _pool(self, X, nb, L):
         """the pooler on the [CLS] rows: X is the last layer's [nb, 768] [CLS] rows (_encode) or

@@ -108,7 +108,7 @@ class _BatchNormAct(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dY):
         x, mask, weight, smean, sinv = ctx.saved_tensors
-        K.side_pump(dY.device, WGRAD_PUMP)  # (encoder INTERLEAVE: its weight-gradient work beside ours)
+        K.side_pump(dY.device)  # (the encoder's flushed weight-gradient work: issued beside ours)
         dY = dY.contiguous(memory_format=torch.channels_last)
         dX = torch.empty_like(x)
         dS = torch.empty_like(x) if ctx.has_skip and ctx.needs_input_grad[3] else None
@@ -215,7 +215,7 @@ class _SyncBatchNormAct(torch.autograd.Function):
     def backward(ctx, dY):
         import torch.distributed as dist
         x, saved, weight, mean, invstd = ctx.saved_tensors
-        K.side_pump(x.device, WGRAD_PUMP)
+        K.side_pump(x.device)
         C = x.shape[1]
         want_w, want_b = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
         bias = ctx.bias_ref
@@ -331,7 +331,6 @@ def _is_stem(w16, stride, padding):
 
 # downsample blocks: conv1's dX epilogue adds the downsample conv's dX (no autograd sum) -- MMU_DS_SINK=0: off
 DS_SINK = os.environ.get("MMU_DS_SINK", "1") != "0"
-WGRAD_PUMP = int(os.environ.get("MMU_WGRAD_PUMP", "1"))  # deferred BERT items issued per BatchNorm backward
 SIDE_WGRAD_MIN_BATCH = int(os.environ.get("MMU_SIDE_WGRAD_MIN_BATCH", "128"))
 
 

@@ -12,7 +12,7 @@ the same classes).  Per ViLT pass (M = B * L token rows, L = text + 1 + patches)
                 (valid patches of the pixel mask, random order / random padding patches drawn
                 by torch.multinomial in the reference's order), interpolated position
                 embeddings, [CLS] + pos[0], + modality[image index]
-  12 x layer    pre-LN ViltLayer = the FLAVA encoder layer (src/flava_encoders._encoder_layers:
+  12 x layer    pre-LN ViltLayer = the FLAVA encoder layer (src/flava_encoders._layer_forward:
                 LN, fused QKV GEMM, mmu_attention_fwd, Wo + residual (f32), LN, W1 + GELU, W2
                 + residual)
   final LN      mmu_layernorm_fwd_f32; pooler tanh(dense(row 0)); classifier head (one row per
@@ -20,12 +20,14 @@ the same classes).  Per ViLT pass (M = B * L token rows, L = text + 1 + patches)
 The residual stream is f32, GEMM operands bf16 with f32 accumulation.  No CPU path: the
 kernels raise on CPU tensors.
 """
+from types import SimpleNamespace
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from . import kernels as K
-from .flava_encoders import _Layer, _encoder_layers, _final_ln, patchify
+from .flava_encoders import _Layer, _encoder_layers, _final_ln, _layer_forward, patchify
 
 bf16 = torch.bfloat16
 MASK_NEG = -10000.0  # additive key mask (exp underflows to 0 exactly like the reference's dtype-min mask)
@@ -96,6 +98,60 @@ def _check_head_dim(cfg, who):
         raise NotImplementedError(f"{who}: hidden_size {cfg.hidden_size} / {cfg.num_attention_heads} heads is not "
                                   "head_dim 64 (mmu_attention_fwd / _bwd)")
 
+
+def _visual_embed(x, pixel_mask, grid, cfg, cls, pos_img, modality_row):
+    """ViltEmbeddings.visual_embed (transformers modeling_vilt) behind the patch GEMM: x [B, gh*gw,
+    H] f32 is the GEMM's output, ``grid`` = (gh, gw); the reference's patch selection and
+    interpolated position embeddings (index bookkeeping on the host, the same torch.multinomial
+    draws in the same order), [CLS] + pos[0], + the modality row -> (rows [B, 1 + n, H], mask).
+    ``cls`` [1, 1, H], ``pos_img`` [1, 1 + P, H] and ``modality_row`` [H] are plain tensors under
+    no_grad (ViltHIP) or the module's parameters (ViltTrainHIP: autograd runs through)."""
+    B, _, H = x.shape
+    gh, gw = grid
+    # pixel mask -> patch mask (nearest), valid extents per sample
+    xm = patch_mask(pixel_mask, gh, gw)
+    x_h = xm.sum(1)[:, 0]
+    x_w = xm.sum(2)[:, 0]
+    pd = cfg.image_size // cfg.patch_size
+    spatial = pos_img[:, 1:, :].transpose(1, 2).reshape(1, H, pd, pd)
+    # one interpolated position grid per distinct valid extent (a batch of full-size
+    # images shares one), gathered per sample
+    ext = [(int(h), int(w)) for h, w in zip(x_h, x_w)]
+    uniq = sorted(set(ext))
+    grids = torch.cat([F.pad(F.interpolate(spatial, size=e, mode="bilinear", align_corners=True),
+                             (0, gw - e[1], 0, gh - e[0])) for e in uniq], 0)
+    grids = grids.flatten(2).transpose(1, 2)  # [U, gh*gw, H]
+    max_len = image_length(xm, cfg.max_image_length)
+    P = gh * gw
+    flat, mask = select_patches(xm.flatten(1), max_len)
+    mask, flat = mask.to(x.device), flat.to(x.device)
+    # F.embedding, not tensor indexing: the indexing backward serialises repeated indices
+    x = F.embedding(flat, x.reshape(B * P, H)).view(B, -1, H)
+    gid = torch.tensor([uniq.index(e) for e in ext], device=x.device)
+    pos = F.embedding((gid * P).repeat_interleave(max_len) + flat % P, grids.reshape(-1, H)).view(B, -1, H)
+    x = torch.cat([cls.expand(B, -1, -1), x], 1)
+    pos = torch.cat([pos_img[:, :1].expand(B, -1, -1), pos], 1)
+    mask = torch.cat([torch.ones(B, 1, dtype=mask.dtype, device=x.device), mask], 1)
+    return x + pos + modality_row, mask
+
+
+def _embed(model, input_ids, attention_mask, token_type_ids, pixel_values, pixel_mask, type_idx):
+    """The start of a ViltModel pass for ViltHIP / ViltTrainHIP (``model._text``, ``model._visual``):
+    mask defaults, text + image rows -> (f32 stream X [B*L, H], additive keymask [B, L], B, L)."""
+    B = input_ids.shape[0]
+    if attention_mask is None:
+        attention_mask = torch.ones_like(input_ids)
+    if pixel_mask is None:
+        pixel_mask = torch.ones(B, pixel_values.shape[-2], pixel_values.shape[-1], device=input_ids.device)
+    txt = model._text(input_ids, token_type_ids)
+    img, img_mask = model._visual(pixel_values, pixel_mask, type_idx)
+    X = torch.cat([txt, img], 1)
+    L, H = X.shape[1], X.shape[2]
+    mask = torch.cat([attention_mask.to(img_mask.dtype), img_mask], 1)
+    keymask = ((1.0 - mask.float()) * MASK_NEG).contiguous()
+    return X.reshape(B * L, H).contiguous(), keymask, B, L
+
+
 class ViltHIP:
     """``ViltForImagesAndTextClassification`` (or a bare ``ViltModel``) on the HIP kernels.
 
@@ -151,9 +207,6 @@ class ViltHIP:
         return X.view(B, Lt, H) + self.modality[0]
 
     def _visual(self, pixel_values, pixel_mask, type_idx):
-        """ViltEmbeddings.visual_embed (transformers modeling_vilt): patch GEMM, then the
-        reference's patch selection and interpolated position embeddings (index bookkeeping on
-        the host, the same torch.multinomial draws in the same order)."""
         B, C, Hh, Ww = pixel_values.shape
         p = self.patch
         gh, gw = Hh // p, Ww // p
@@ -162,50 +215,16 @@ class ViltHIP:
         x = torch.empty(B * gh * gw, H, dtype=torch.float32, device=rows.device)
         K.gemm(rows, rows.shape[1], True, self.w_patch, rows.shape[1], True, x, H, B * gh * gw, H, rows.shape[1],
                epi=K.epilogue(K.EPI_STORE, bias=self.b_patch))
-        x = x.view(B, gh * gw, H)
-        # pixel mask -> patch mask (nearest), valid extents per sample
-        xm = patch_mask(pixel_mask, gh, gw)
-        x_h = xm.sum(1)[:, 0]
-        x_w = xm.sum(2)[:, 0]
-        pd = self.config.image_size // self.config.patch_size
-        spatial = self.pos_img[:, 1:, :].transpose(1, 2).reshape(1, H, pd, pd)
-        # one interpolated position grid per distinct valid extent (a batch of full-size
-        # images shares one), gathered per sample
-        ext = [(int(h), int(w)) for h, w in zip(x_h, x_w)]
-        uniq = sorted(set(ext))
-        grids = torch.cat([F.pad(F.interpolate(spatial, size=e, mode="bilinear", align_corners=True),
-                                 (0, gw - e[1], 0, gh - e[0])) for e in uniq], 0)
-        grids = grids.flatten(2).transpose(1, 2)  # [U, gh*gw, H]
-        max_len = image_length(xm, self.config.max_image_length)
-        P = gh * gw
-        flat, mask = select_patches(xm.flatten(1), max_len)
-        mask = mask.to(x.device)
-        flat = flat.to(x.device)
-        x = x.reshape(B * P, H)[flat].view(B, -1, H)
-        gid = torch.tensor([uniq.index(e) for e in ext], device=x.device)
-        pos = grids.reshape(-1, H)[(gid * P).repeat_interleave(max_len) + flat % P].view(B, -1, H)
-        x = torch.cat([self.cls.expand(B, -1, -1), x], 1)
-        pos = torch.cat([self.pos_img[:, :1].expand(B, -1, -1), pos], 1)
-        mask = torch.cat([torch.ones(B, 1, dtype=mask.dtype, device=x.device), mask], 1)
-        return x + pos + self.modality[type_idx], mask
+        return _visual_embed(x.view(B, gh * gw, H), pixel_mask, (gh, gw), self.config, self.cls, self.pos_img,
+                             self.modality[type_idx])
 
     # ------------------------------------------------------------------ forward
     @torch.no_grad()
     def vilt(self, input_ids, attention_mask, token_type_ids, pixel_values, pixel_mask, type_idx=1):
         """ViltModel.forward -> (last_hidden_state [B, L, H] f32, pooler_output [B, H])"""
         K._dev_check(input_ids)
-        B, Lt = input_ids.shape
-        if attention_mask is None:
-            attention_mask = torch.ones_like(input_ids)
-        if pixel_mask is None:
-            pixel_mask = torch.ones(B, pixel_values.shape[-2], pixel_values.shape[-1], device=input_ids.device)
-        txt = self._text(input_ids, token_type_ids)
-        img, img_mask = self._visual(pixel_values, pixel_mask, type_idx)
-        X = torch.cat([txt, img], 1)
-        L, H = X.shape[1], X.shape[2]
-        mask = torch.cat([attention_mask.to(img_mask.dtype), img_mask], 1)
-        keymask = ((1.0 - mask.float()) * MASK_NEG).contiguous()
-        X = _encoder_layers(X.reshape(B * L, H).contiguous(), keymask, self.layers, B, L)
+        X, keymask, B, L = _embed(self, input_ids, attention_mask, token_type_ids, pixel_values, pixel_mask, type_idx)
+        X = _encoder_layers(X, keymask, self.layers, B, L)
         seq = _final_ln(X, self.final_ln, B, L)
         pooled = torch.tanh(F.linear(seq[:, 0], self.pool_w, self.pool_b))
         return seq, pooled
@@ -238,8 +257,8 @@ class ViltHIP:
 #   text embed    torch (gathers + LayerNorm in f32: 0.1 ms of a step)
 #   patch embed   mmu_gemm (32x32 / 32 patch Conv2d as one GEMM; weight grad mmu_gemm, bias grad
 #                 mmu_colsum), the reference's patch selection / interpolated positions in torch
-#   12 x layer    _ViltLayerFunction: the inference layer (f32 residual stream, bf16 GEMM
-#                 operands) plus its backward -- DGELU-epilogue data grads, f32 weight grads,
+#   12 x layer    _ViltLayerFunction: the inference layer (flava_encoders._layer_forward with
+#                 save: f32 residual stream, bf16 GEMM operands) plus its backward -- DGELU-epilogue data grads, f32 weight grads,
 #                 mmu_attention_bwd (+ fused Q/K/V bias grads), mmu_layernorm_bwd_f32; the stream
 #                 gradient stays f32
 #   final LN, pooler, classifier, loss   torch f32 on the [CLS] rows
@@ -276,31 +295,13 @@ class _ViltLayerFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, X, keymask, B, L, heads, eps1, eps2, wq, wk, wv, bq, bk, bv, wo, bo, l1w, l1b, w1, b1, w2, b2,
                 l2w, l2b):
-        M, H = X.shape
-        Fd = w1.shape[0]
-        dev, f32 = X.device, torch.float32
         Wqkv = torch.cat([wq, wk, wv]).to(bf16).contiguous()
         bqkv = torch.cat([bq, bk, bv]).float().contiguous()
         Wo, W1, W2 = (w.to(bf16).contiguous() for w in (wo, w1, w2))
-        h1 = torch.empty(M, H, dtype=bf16, device=dev)
-        m1, r1 = torch.empty(M, dtype=f32, device=dev), torch.empty(M, dtype=f32, device=dev)
-        K.layernorm_fwd_f32(X, l1w, l1b, h1, None, m1, r1, eps=eps1)
-        qkv = torch.empty(M, 3 * H, dtype=bf16, device=dev)
-        K.gemm(h1, H, True, Wqkv, H, True, qkv, 3 * H, M, 3 * H, H, epi=K.epilogue(K.EPI_STORE, bias=bqkv))
-        O = torch.empty(M, H, dtype=bf16, device=dev)
-        lse = torch.empty(B * heads, L, dtype=f32, device=dev)
-        K.attention_fwd(qkv, keymask, O, lse, B, L, heads, 0.0, 0, None)
-        S = torch.empty(M, H, dtype=f32, device=dev)
-        K.gemm(O, H, True, Wo, H, True, S, H, M, H, H, epi=K.epilogue(K.EPI_BIAS_DROP_RES, bias=bo, residual=X))
-        h2 = torch.empty(M, H, dtype=bf16, device=dev)
-        m2, r2 = torch.empty(M, dtype=f32, device=dev), torch.empty(M, dtype=f32, device=dev)
-        K.layernorm_fwd_f32(S, l2w, l2b, h2, None, m2, r2, eps=eps2)
-        G = torch.empty(M, Fd, dtype=bf16, device=dev)
-        Z = torch.empty(M, Fd, dtype=bf16, device=dev)  # gelu'(.) for the backward's DGELU epilogue
-        K.gemm(h2, H, True, W1, H, True, G, Fd, M, Fd, H, epi=K.epilogue(K.EPI_BIAS_GELU, bias=b1, aux=Z))
-        Y = torch.empty(M, H, dtype=f32, device=dev)
-        K.gemm(G, Fd, True, W2, Fd, True, Y, H, M, H, Fd, epi=K.epilogue(K.EPI_BIAS_DROP_RES, bias=b2, residual=S))
-        ctx.save_for_backward(X, keymask, h1, m1, r1, qkv, O, lse, S, h2, m2, r2, G, Z, Wqkv, Wo, W1, W2, l1w, l2w)
+        lw = SimpleNamespace(wqkv=Wqkv, bqkv=bqkv, wo=Wo, bo=bo, w1=W1, b1=b1, w2=W2, b2=b2, ln1=(l1w, l1b, eps1),
+                             ln2=(l2w, l2b, eps2), heads=heads)
+        Y, kept = _layer_forward(X, keymask, lw, B, L, save=True)  # (h1, m1, r1, qkv, O, lse, S, h2, m2, r2, G, Z)
+        ctx.save_for_backward(X, keymask, *kept, Wqkv, Wo, W1, W2, l1w, l2w)
         ctx.meta = (B, L, heads)
         return Y
 
@@ -382,7 +383,11 @@ class ViltTrainHIP(nn.Module):
         self.model = model
         self.config = cfg
 
-    def _text(self, emb, input_ids, token_type_ids):
+    def _vilt(self):
+        return self.model.vilt if hasattr(self.model, "vilt") else self.model
+
+    def _text(self, input_ids, token_type_ids):
+        emb = self._vilt().embeddings
         te = emb.text_embeddings
         Lt = input_ids.shape[1]
         if token_type_ids is None:
@@ -395,52 +400,21 @@ class ViltTrainHIP(nn.Module):
         X = F.layer_norm(E.float(), (E.shape[-1],), ln.weight, ln.bias, ln.eps)
         return X + emb.token_type_embeddings.weight[0]
 
-    def _visual(self, emb, pixel_values, pixel_mask, type_idx):
-        cfg = self.config
+    def _visual(self, pixel_values, pixel_mask, type_idx):
+        emb = self._vilt().embeddings
         B, C, Hh, Ww = pixel_values.shape
         proj = emb.patch_embeddings.projection
         p = proj.kernel_size[0]
         gh, gw = Hh // p, Ww // p
-        H = proj.weight.shape[0]
         rows = patchify(pixel_values.float(), p).to(bf16).contiguous()
-        x = _PatchGemm.apply(rows, proj.weight, proj.bias).view(B, gh * gw, H)
-        xm = patch_mask(pixel_mask, gh, gw)
-        x_h, x_w = xm.sum(1)[:, 0], xm.sum(2)[:, 0]
-        pd = cfg.image_size // cfg.patch_size
-        pos_img = emb.position_embeddings
-        spatial = pos_img[:, 1:, :].transpose(1, 2).reshape(1, H, pd, pd)
-        ext = [(int(h), int(w)) for h, w in zip(x_h, x_w)]
-        uniq = sorted(set(ext))
-        grids = torch.cat([F.pad(F.interpolate(spatial, size=e, mode="bilinear", align_corners=True),
-                                 (0, gw - e[1], 0, gh - e[0])) for e in uniq], 0)
-        grids = grids.flatten(2).transpose(1, 2)
-        max_len = image_length(xm, cfg.max_image_length)
-        P = gh * gw
-        flat, mask = select_patches(xm.flatten(1), max_len)
-        mask, flat = mask.to(x.device), flat.to(x.device)
-        x = F.embedding(flat, x.reshape(B * P, H)).view(B, -1, H)
-        gid = torch.tensor([uniq.index(e) for e in ext], device=x.device)
-        pos = F.embedding((gid * P).repeat_interleave(max_len) + flat % P, grids.reshape(-1, H)).view(B, -1, H)
-        x = torch.cat([emb.cls_token.expand(B, -1, -1), x], 1)
-        pos = torch.cat([pos_img[:, :1].expand(B, -1, -1), pos], 1)
-        mask = torch.cat([torch.ones(B, 1, dtype=mask.dtype, device=x.device), mask], 1)
-        return x + pos + emb.token_type_embeddings.weight[type_idx], mask
+        x = _PatchGemm.apply(rows, proj.weight, proj.bias).view(B, gh * gw, -1)
+        return _visual_embed(x, pixel_mask, (gh, gw), self.config, emb.cls_token, emb.position_embeddings,
+                             emb.token_type_embeddings.weight[type_idx])
 
     def _pooled(self, input_ids, attention_mask, token_type_ids, pixel_values, pixel_mask, type_idx):
-        vm = self.model.vilt if hasattr(self.model, "vilt") else self.model
-        emb = vm.embeddings
-        B = input_ids.shape[0]
-        if attention_mask is None:
-            attention_mask = torch.ones_like(input_ids)
-        if pixel_mask is None:
-            pixel_mask = torch.ones(B, pixel_values.shape[-2], pixel_values.shape[-1], device=input_ids.device)
-        txt = self._text(emb, input_ids, token_type_ids)
-        img, img_mask = self._visual(emb, pixel_values, pixel_mask, type_idx)
-        X = torch.cat([txt, img], 1)
-        L, H = X.shape[1], X.shape[2]
-        mask = torch.cat([attention_mask.to(img_mask.dtype), img_mask], 1)
-        keymask = ((1.0 - mask.float()) * MASK_NEG).contiguous()
-        X = X.reshape(B * L, H).contiguous()
+        vm = self._vilt()
+        X, keymask, B, L = _embed(self, input_ids, attention_mask, token_type_ids, pixel_values, pixel_mask, type_idx)
+        H = X.shape[1]
         for lyr in vm.encoder.layer:
             a = lyr.attention.attention
             X = _ViltLayerFunction.apply(

@@ -8,7 +8,10 @@ architecture (dandelin/vilt-b32-mlm is not offline), 2 layers, 64 x 64 images (4
 Bars, written before the first run: loss within 1e-2 relative; logits within 1e-2 of max|logit|;
 per-parameter-tensor gradient error ||g_hip - g_ref|| / ||g_ref|| with median <= 1e-2 and 90th
 percentile <= 5e-2.  One AdamW step on each is printed as a diagnostic only (Adam's first step
-is lr * sign(g) per element, so near-zero gradients flip their element's update on noise)."""
+is lr * sign(g) per element, so near-zero gradients flip their element's update on noise).
+
+The training layer's forward and the inference layer (src/flava_encoders._layer_forward with and
+without ``save``) must stay one computation: one ViltLayer through both, equal bit for bit."""
 import copy
 
 import pytest
@@ -92,6 +95,39 @@ def test_vilt_train_step_matches_transformers(dev, partial):
     dh = torch.cat([(a.detach() - b).flatten() for a, b in zip(hip_model.parameters(), p0)])
     upd = ((dh - du).norm() / du.norm()).item()
     print(f"  AdamW first-step update rel err {upd:.2e} (diagnostic)")
+
+
+def test_train_layer_forward_is_the_inference_layer_bit_for_bit(dev):
+    """The training layer (_ViltLayerFunction, which also stores the LayerNorm statistics and gelu'(.)
+    for its backward) and the inference layer (flava_encoders._encoder_layers) are one computation:
+    one default-width ViltLayer, B = 3, L = 70 (a full 64-key tile + a 6-key tail, one partial query
+    block), the last 5 keys of one sample masked; the f32 output streams are equal as bits."""
+    from transformers import ViltConfig
+    from transformers.models.vilt.modeling_vilt import ViltLayer
+    from src.flava_encoders import _Layer, _encoder_layers
+    from src.vilt import MASK_NEG, _ViltLayerFunction
+    torch.manual_seed(0)
+    lyr = ViltLayer(ViltConfig()).to(dev)
+    B, L, H = 3, 70, lyr.output.dense.out_features
+    X = torch.randn(B * L, H, generator=torch.Generator().manual_seed(5)).to(dev)
+    keymask = torch.zeros(B, L, device=dev)
+    keymask[1, L - 5:] = MASK_NEG
+    a = lyr.attention.attention
+    with torch.no_grad():
+        inf = _encoder_layers(X, keymask, [_Layer(lyr, dev)], B, L)
+        trn = _ViltLayerFunction.apply(
+            X, keymask, B, L, a.num_attention_heads, lyr.layernorm_before.eps, lyr.layernorm_after.eps,
+            a.query.weight, a.key.weight, a.value.weight, a.query.bias, a.key.bias, a.value.bias,
+            lyr.attention.output.dense.weight, lyr.attention.output.dense.bias,
+            lyr.layernorm_before.weight, lyr.layernorm_before.bias,
+            lyr.intermediate.dense.weight, lyr.intermediate.dense.bias,
+            lyr.output.dense.weight, lyr.output.dense.bias,
+            lyr.layernorm_after.weight, lyr.layernorm_after.bias)
+    torch.cuda.synchronize()
+    assert inf.dtype == trn.dtype == torch.float32 and inf.shape == trn.shape == (B * L, H)
+    assert torch.isfinite(inf).all() and not torch.equal(inf, X)
+    differ = (inf.view(torch.int32) != trn.view(torch.int32)).sum().item()
+    assert differ == 0, f"{differ} of {inf.numel()} elements differ between the training and the inference layer"
 
 
 def test_vilt_train_refuses_dropout(dev):
