@@ -89,6 +89,7 @@ static __device__ __forceinline__ bf16x8 row_frag(const char* s, int row0, int k
 }
 // transposed fragment matching an accumulator used as the other operand: lane l holds
 // tile[row0 + 16s + 8(j>>2) + 4h + (j&3)][col0 + (l&31)], h = l>>5  (row0 includes 16s)
+// (the builtin: only the forward still reads this way, see tr_issue below)
 static __device__ __forceinline__ bf16x8 tr_frag(const char* s, int row0, int col0, int l) {
   const int g = l >> 4, i = l & 15, q = i >> 2, p = i & 3, h = g >> 1;
   const int col = col0 + 16 * (g & 1) + 4 * p;  // element column
@@ -100,6 +101,29 @@ static __device__ __forceinline__ bf16x8 tr_frag(const char* s, int row0, int co
   bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((MMU_LDS(bf16x4)*)a1);
   return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
+// The backward kernels' tiles are staged by a 3- and a 4-deep LDS-DMA ring, so there the two
+// ds_read_b64_tr_b16 go through the asm helpers of mmu_common.h (the builtin drains the ring in
+// front of the first read of every tile; tools/isa_dma_waits.py checks it).  The forward keeps the
+// builtin: its ring is 2 deep with a full wait per tile, and the asm reads measured no gain there
+// (profiles/dma_overlap_ab.txt).  tr_issue issues the reads for the tile at s + BASE (the stage /
+// tile base and the rows ROW0, ROW0 + 8 are the instructions' immediates; ROW0 % 16 == 0, so
+// 4h + q stays within an 8-row group), the caller waits (lds_wait) and then takes the fragment
+// with tr_get
+struct TrPair {
+  bf16x4 lo, hi;
+};
+template <int BASE, int ROW0, int COL0>
+static __device__ __forceinline__ TrPair tr_issue(const char* s, int l) {
+  const int g = l >> 4, i = l & 15, q = i >> 2, p = i & 3, h = g >> 1;
+  const int cb = (COL0 + 16 * (g & 1) + 4 * p) * 2;  // element column, in bytes
+  const int rl = 4 * h + q;
+  const char* r = s + rl * 128 + (cb & 15);
+  TrPair t;
+  t.lo = lds_tr16<BASE + ROW0 * 128>(r + (((cb >> 4) ^ fsw(ROW0 + rl)) << 4));
+  t.hi = lds_tr16<BASE + (ROW0 + 8) * 128>(r + (((cb >> 4) ^ fsw(ROW0 + 8 + rl)) << 4));
+  return t;
+}
+static __device__ __forceinline__ bf16x8 tr_get(const TrPair& t) { return lds_landed(t.lo, t.hi); }
 // 8 accumulator registers (8s..8s+7) -> bf16 operand fragment
 static __device__ __forceinline__ bf16x8 acc_frag(const f32x16& a, int s) {
   bf16x8 r;
@@ -625,6 +649,18 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void a
         sc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(Qs, 0, ks, l), kf[ks], sc, 0, 0, 0);
         dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag(Ds, 0, ks, l), vf[ks], dp, 0, 0, 0);
       }
+      // the dO / Q fragments of the dV / dK MFMAs (transposed, asm reads): issued ahead of the
+      // exponentials, waited for behind them
+      constexpr int QB = SG * DK_STAGE, DB = SG * DK_STAGE + DK_TILE;
+      TrPair dt_[2][2], qt_[2][2];  // [16-row half][32-column half], in the order of their use
+      dt_[0][0] = tr_issue<DB, 0, 0>(smem, l);
+      qt_[0][0] = tr_issue<QB, 0, 0>(smem, l);
+      dt_[0][1] = tr_issue<DB, 0, 32>(smem, l);
+      qt_[0][1] = tr_issue<QB, 0, 32>(smem, l);
+      dt_[1][0] = tr_issue<DB, 16, 0>(smem, l);
+      qt_[1][0] = tr_issue<QB, 16, 0>(smem, l);
+      dt_[1][1] = tr_issue<DB, 16, 32>(smem, l);
+      qt_[1][1] = tr_issue<QB, 16, 32>(smem, l);
       f32x16 pz;  // dropped P / zs (for dV)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -638,6 +674,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void a
           sc[r] = pr * dp[r];
         }
       }
+      lds_wait<0>();  // (all 16 reads, also when the second half is skipped below)
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
         // a last query tile whose live rows all sit in its first 16 (L = 513: one) skips the
@@ -646,8 +683,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void a
         bf16x8 pf = acc_frag(pz, s2), sf = acc_frag(sc, s2);
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt) {
-          dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pf, tr_frag(Ds, 16 * s2, 32 * dt, l), dv[dt], 0, 0, 0);
-          dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sf, tr_frag(Qs, 16 * s2, 32 * dt, l), dk[dt], 0, 0, 0);
+          dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pf, tr_get(dt_[s2][dt]), dv[dt], 0, 0, 0);
+          dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sf, tr_get(qt_[s2][dt]), dk[dt], 0, 0, 0);
         }
       }
     }
@@ -816,17 +853,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
     const char* Ks = st;
     const char* Vs = st + DQ_TILE;
     const float* mk = (const float*)(st + 2 * DQ_TILE);
-    const uint32_t* kwords = (const uint32_t*)(st + 2 * DQ_TILE + 256 + w * 256);  // [32 rows][lo, hi]
     if (wave_live) {
       // keep bits of this lane's query row, pre-shifted by 4h (as in attn_dq_kernel)
-      const uint64_t kw = drop ? ((uint64_t)kwords[2 * (l & 31) + 1] << 32 | kwords[2 * (l & 31)]) : ~0ull;
-      const uint64_t kwh = kw >> (4 * h);
-#pragma unroll
-      for (int st2 = 0; st2 < 2; ++st2) {
+      // (an asm read as well: through a plain load hipcc drains the DMA ring in front of it.
+      // Without dropout the words are the zeros of an empty buffer and are not used.)
+      // [4 waves][32 rows][lo, hi] behind the mask row
+      uint64_t kw_raw = lds_read64<SG * DQ_STAGE + 2 * DQ_TILE + 256>(smem + w * 256 + 8 * (l & 31));
+      uint64_t kwh = 0;
+      auto half = [&](auto st2_tag) {
+        constexpr int st2 = decltype(st2_tag)::value;
         // a last tile whose live keys all sit in its first half (L = 513: one) skips the second:
         // its K / V rows are the zeros past L, which add exactly nothing to dQ
-        if (st2 == 1 && 64 * j + 32 >= L) break;
-        const uint32_t kw32 = (uint32_t)(kwh >> (32 * st2));
+        if (st2 == 1 && 64 * j + 32 >= L) return;
+        // this half's K fragments of the dQ MFMAs (transposed, asm reads): issued ahead of the
+        // S / dP MFMAs and the exponentials, waited for behind them
+        TrPair kt[2][2];
+        kt[0][0] = tr_issue<SG * DQ_STAGE, 32 * st2, 0>(smem, l);
+        kt[0][1] = tr_issue<SG * DQ_STAGE, 32 * st2, 32>(smem, l);
+        kt[1][0] = tr_issue<SG * DQ_STAGE, 32 * st2 + 16, 0>(smem, l);
+        kt[1][1] = tr_issue<SG * DQ_STAGE, 32 * st2 + 16, 32>(smem, l);
         // S starts at the mask: register r holds key kl = 32 st2 + 8 (r >> 2) + 4 h + (r & 3),
         // so each group of 4 registers takes 4 contiguous mask entries (one f32x4 read)
         f32x16 sc, dp;
@@ -848,6 +893,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
         // dp started at -delta/zs; the keep bit becomes an all-ones / zero mask (v_bfe_i32) that
         // bit-selects it against -delta/zs (without dropout kw is all ones).  The zs of dS goes
         // into dQ's final scale.
+        lds_wait<0>();
+        if (st2 == 0) kwh = (drop ? lds_landed64(kw_raw) : ~0ull) >> (4 * h);
+        const uint32_t kw32 = (uint32_t)(kwh >> (32 * st2));
         auto one = [&](auto r_tag) {
           constexpr int r = decltype(r_tag)::value;
           const float pr = __builtin_amdgcn_exp2f(fmaf(sc[r], LOG2E, nlse2));
@@ -860,10 +908,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
           bf16x8 sf = acc_frag(sc, s2);
 #pragma unroll
           for (int dt = 0; dt < 2; ++dt)
-            dq[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag(Ks, 32 * st2 + 16 * s2, 32 * dt, l), sf, dq[dt],
-                                                             0, 0, 0);
+            dq[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_get(kt[s2][dt]), sf, dq[dt], 0, 0, 0);
         }
-      }
+      };
+      half(std::integral_constant<int, 0>{});
+      half(std::integral_constant<int, 1>{});
     }
     };
   for (int j0 = 0; j0 < nkv; j0 += DQ_NS) {

@@ -22,10 +22,13 @@
 #include "mmu_common.h"
 #include "mmu_internal.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace mmu {
 
 constexpr int BKT = 64;
+template <int N>
+using ic = std::integral_constant<int, N>;  // a compile-time index as a function argument
 
 // Diagnostic build only (make EXTRA=-DMMU_GEMM_STAMPS OUT=../../ab/stamps.so): wave 0 of every
 // big-kernel workgroup records s_memtime at start, after the first K-tile landed, after the
@@ -92,6 +95,86 @@ static __device__ __forceinline__ bf16x8 s_frag(const char* s, int row0, int ks,
     bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((MMU_LDS(bf16x4)*)a0);
     bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((MMU_LDS(bf16x4)*)a1);
     return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+  }
+}
+
+// The two halves of s_frag<false, ROWB> issued as asm reads (mmu_common.h: beside LDS-DMA the
+// builtin drains the ring), for the k-step KS of the tile at s + BASE: 32 KS ROWB + BASE and the
+// 4 k-rows between the halves (k1's swizzle is k0's ^ 4) are the instruction's immediate
+template <int ROWB, int KS, int BASE>
+static __device__ __forceinline__ void s_frag_tr_issue(const char* s, int row0, int l, bf16x4& lo, bf16x4& hi) {
+  const int g = l >> 4, i = l & 15, q = i >> 2, p = i & 3;
+  const int b = row0 >> 4;
+  const int k0 = 8 * g + q;
+  const char* r = s + k0 * ROWB + 8 * p;
+  lo = lds_tr16<BASE + 32 * KS * ROWB>(r + ((b ^ sw_mn(k0)) << 5));
+  hi = lds_tr16<BASE + (32 * KS + 4) * ROWB>(r + ((b ^ sw_mn(k0) ^ 4) << 5));
+}
+
+// one 32-deep k-step of the 256x256 body: 4 B and 8 A fragments, 32 MFMAs.  An M/N-major operand
+// is read transposed through the asm helpers: all its reads are issued first, then a ladder of
+// counted waits releases the MFMAs fragment by fragment (A fragments outermost when A is
+// transposed, else B fragments).  The sched_barrier after each rung keeps its MFMAs above the next
+// wait (left alone, hipcc sinks them below the last one: one full wait per k-step; measured equal
+// on the large weight gradients, 3-5 % slower on the 768 x 768 one).  Each accumulator still sees
+// its k-steps in order, so the sums are those of the plain i, j loop.
+template <bool AK, bool BKM, int KS>
+static __device__ __forceinline__ void big_kstep(const char* sa, int wm, int wn, int l, f32x4 (&acc)[4][8]) {
+  constexpr int B_OFF = 256 * BKT * 2;  // the B tile follows the A tile (B_TILE)
+  bf16x8 fb[4], fa[8];
+  if constexpr (AK && BKM) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) fb[i] = s_frag<true, 512>(sa + B_OFF, 64 * wn + 16 * i, KS, l);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) fa[j] = s_frag<true, 512>(sa, 128 * wm + 16 * j, KS, l);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[i], fa[j], acc[i][j], 0, 0, 0);
+  } else {
+    bf16x4 blo[4], bhi[4], alo[8], ahi[8];
+    if constexpr (!BKM) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) s_frag_tr_issue<512, KS, B_OFF>(sa, 64 * wn + 16 * i, l, blo[i], bhi[i]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) fb[i] = s_frag<true, 512>(sa + B_OFF, 64 * wn + 16 * i, KS, l);
+    }
+    if constexpr (!AK) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) s_frag_tr_issue<512, KS, 0>(sa, 128 * wm + 16 * j, l, alo[j], ahi[j]);
+      // 2 reads per fragment, A's 16 issued last: fragment j has landed at lgkmcnt(14 - 2j),
+      // and with it everything issued before A
+      auto step = [&](auto jc, auto nc) {
+        constexpr int j = decltype(jc)::value;
+        lds_wait<decltype(nc)::value>();
+        if constexpr (j == 0 && !BKM) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) fb[i] = lds_landed(blo[i], bhi[i]);
+        }
+        fa[j] = lds_landed(alo[j], ahi[j]);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[i], fa[j], acc[i][j], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      step(ic<0>{}, ic<14>{}); step(ic<1>{}, ic<12>{}); step(ic<2>{}, ic<10>{}); step(ic<3>{}, ic<8>{});
+      step(ic<4>{}, ic<6>{});  step(ic<5>{}, ic<4>{});  step(ic<6>{}, ic<2>{});  step(ic<7>{}, ic<0>{});
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) fa[j] = s_frag<true, 512>(sa, 128 * wm + 16 * j, KS, l);
+      auto step = [&](auto icn, auto nc) {  // B's 8 reads: fragment i has landed at lgkmcnt(6 - 2i)
+        constexpr int i = decltype(icn)::value;
+        lds_wait<decltype(nc)::value>();
+        fb[i] = lds_landed(blo[i], bhi[i]);
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[i], fa[j], acc[i][j], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      step(ic<0>{}, ic<6>{}); step(ic<1>{}, ic<4>{}); step(ic<2>{}, ic<2>{}); step(ic<3>{}, ic<0>{});
+    }
   }
 }
 
@@ -748,26 +831,14 @@ static __device__ __forceinline__ void gemm_big_body(const GemmParams& p) {
   GEMM_STAMP(1);
   for (int kt = 0; kt < nk; ++kt) {
     const char* sa = smem + (kt & 1) * B_STAGE;
-    const char* sb = sa + B_TILE;
     if (kt + 1 < nk) {
       char* d = smem + ((kt + 1) & 1) * B_STAGE;
       const int64_t k1 = kb + (int64_t)(kt + 1) * BKT;
       dma_a(d, k1);
       dma_b(d + B_TILE, k1);
     }
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 fb[4], fa[8];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) fb[i] = s_frag<BKM, 512>(sb, 64 * wn + 16 * i, ks, l);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) fa[j] = s_frag<AK, 512>(sa, 128 * wm + 16 * j, ks, l);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[i], fa[j], acc[i][j], 0, 0, 0);
-    }
+    big_kstep<AK, BKM, 0>(sa, wm, wn, l, acc);
+    big_kstep<AK, BKM, 1>(sa, wm, wn, l, acc);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }

@@ -17,6 +17,45 @@ typedef uint16_t u16x8 __attribute__((ext_vector_type(8)));
 static __device__ __forceinline__ float bf2f(bf16 x) { return (float)x; }
 static __device__ __forceinline__ bf16 f2bf(float x) { return (bf16)x; }
 
+// ---------------------------------------------------------------- transposed LDS reads beside LDS-DMA
+// In a loop that stages tiles with buffer_load ... lds, a ds_read_b64_tr_b16 issued through the
+// builtin makes hipcc wait vmcnt(0) first: it cannot tell the ring stage being read from the one
+// being filled, so every DMA in flight is drained in the middle of the loop body and fill and
+// MFMA run back to back.  Such reads therefore go through these asm helpers (the compiler neither
+// waits vmcnt for them nor counts them in lgkmcnt), and tools/isa_dma_waits.py checks the .s:
+//   lo = lds_tr16<OFF>(a); ...      issue (a = the address without its compile-time part OFF)
+//   lds_wait<N>();                  at most N LDS reads still in flight (LDS returns in order)
+//   f = lds_landed(lo, hi);         every use of f is scheduled below that wait
+// The three are volatile asm statements, which keep their order among themselves.  hipcc pads no
+// wait states around them either; none are needed: the destination is written when the LDS data
+// returns, tens of cycles after issue, past the operand reads of any MFMA issued before the read
+// (hipcc's own ds_reads reuse an MFMA's A / B registers the same way), and the consumer sits
+// behind lds_wait, where hipcc treats lds_landed's operands as freshly written.
+template <int OFF>
+static __device__ __forceinline__ bf16x4 lds_tr16(const char* a) {
+  bf16x4 r;
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"((MMU_LDS(const char)*)a), "n"(OFF));
+  return r;
+}
+template <int N>
+static __device__ __forceinline__ void lds_wait() {
+  asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N));
+}
+template <int OFF>  // a plain 8-byte LDS read, the same way (8-byte aligned address)
+static __device__ __forceinline__ uint64_t lds_read64(const char* a) {
+  uint64_t r;
+  asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(r) : "v"((MMU_LDS(const char)*)a), "n"(OFF));
+  return r;
+}
+static __device__ __forceinline__ uint64_t lds_landed64(uint64_t v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+static __device__ __forceinline__ bf16x8 lds_landed(bf16x4 lo, bf16x4 hi) {
+  asm volatile("" : "+v"(lo), "+v"(hi));
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
 // ---------------------------------------------------------------- counter-based RNG
 // SplitMix64 finaliser of (seed + ctr * golden): stateless, so forward and backward
 // regenerate the same dropout mask from (seed, element counter).
