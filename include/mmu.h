@@ -74,6 +74,11 @@ int mmu_get_deterministic(void);
  * ImageBertEmbeddings.img_embeddings (src/mmbt.py:51,71).
  * Constraints: N % 128 == 0; K % 64 == 0 when an operand is K-major;
  *              M % 128 == 0 when A is M-major (not K-major).
+ * Alignment (refused otherwise: the kernels access all of these as 16-B vectors): A, B, C, the
+ * residual, aux, bias, res_ln_w / res_ln_b, bn_x, bn_mean and the float2 tables 16-B aligned;
+ * lda, ldb, ldx and the ldc / ldr of bf16 rows multiples of 8, those of f32 rows multiples of 4;
+ * for batch > 1 every batch stride a multiple of the same.  The plain colsum and res_ln_mean /
+ * res_ln_rstd need 4 B only.
  */
 enum {
   MMU_EPI_STORE = 0,        /* C = acc (+bias[n]) (+C if accumulate)                     */

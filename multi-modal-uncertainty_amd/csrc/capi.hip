@@ -218,6 +218,44 @@ static int gemm_impl(const void* A, int64_t lda, int a_kmajor, const void* B, in
     return fail("mmu_gemm: res_mask only with ADD_RES / ADD_RES_BNB, batch 1, ldr == N");
   if (p.accumulate && c_dtype != MMU_F32) return fail("mmu_gemm: accumulate needs f32 C");
   if (p.drop_p < 0.f || p.drop_p >= 1.f) return fail("mmu_gemm: drop_p out of range");
+  // Every access of the kernels below is a 16-B vector at a column that is a multiple of 8: the
+  // operand tiles (uint4 / 16-B buffer loads), C (bf16x8, or two float4), residual and aux rows
+  // (bf16x8; float4 for the f32 hidden stream), bias / res_ln_w / res_ln_b / bn_mean (float4) and the
+  // float2 tables (float4 per column pair).  So each base, each leading dimension and, for
+  // batch > 1, each batch stride must keep 16 B.  (The plain colsum is reached by 4-B atomics and
+  // scalar folds only, res_ln_mean / res_ln_rstd by scalar loads, the masks by byte loads.)
+  {
+    const bool bat = batch > 1;
+    auto off16 = [](const void* q) { return ((uintptr_t)q & 15) != 0; };
+    const bool cf32 = c_dtype == MMU_F32;
+    if (off16(A) || off16(B) || off16(C)) return fail("mmu_gemm: A, B and C must be 16-B aligned");
+    if (!cf32 && ldc % 8) return fail("mmu_gemm: ldc=%ld of a bf16 C must be a multiple of 8", ldc);
+    if (bat && (strideA % 8 || strideB % 8 || strideC % (cf32 ? 4 : 8)))
+      return fail("mmu_gemm: batch strides must keep the operands 16-B aligned");
+    const bool uses_res = kind == MMU_EPI_BIAS_DROP_RES || kind == MMU_EPI_ADD_RES || kind == MMU_EPI_ADD_RES_BNB;
+    if (uses_res) {
+      const int64_t rq = (kind == MMU_EPI_BIAS_DROP_RES && cf32) ? 4 : 8;  // elements per 16 B
+      if (off16(p.residual) || p.ldr % rq || (bat && p.res_bstride % rq))
+        return fail("mmu_gemm: residual, ldr=%ld and res_bstride must keep 16-B alignment", p.ldr);
+    }
+    const bool uses_aux = p.aux && (kind == MMU_EPI_BIAS_GELU || kind == MMU_EPI_DGELU || kind == MMU_EPI_BIAS_DROP_QGELU);
+    if (uses_aux && (off16(p.aux) || p.ldx % 8 || (bat && p.aux_bstride % 8)))
+      return fail("mmu_gemm: aux, ldx=%ld and aux_bstride must keep 16-B alignment", p.ldx);
+    const bool uses_bias = p.bias && kind != MMU_EPI_DGELU && kind != MMU_EPI_ADD_RES;
+    if (uses_bias && (off16(p.bias) || (bat && p.bias_bstride % 4)))
+      return fail("mmu_gemm: bias and bias_bstride must keep 16-B alignment");
+    if (p.res_ln_w && (off16(p.res_ln_w) || off16(p.res_ln_b) || (bat && p.res_ln_bstride % 4)))
+      return fail("mmu_gemm: res_ln_w, res_ln_b and res_ln_bstride must keep 16-B alignment");
+    if (p.res_ln_w && (((uintptr_t)p.res_ln_mean | (uintptr_t)p.res_ln_rstd) & 3))
+      return fail("mmu_gemm: res_ln_mean / res_ln_rstd must be 4-B aligned");
+    const bool table = kind == MMU_EPI_STORE_STATS || kind == MMU_EPI_STORE_BNB || kind == MMU_EPI_ADD_RES_BNB;
+    if (table && off16(p.colsum)) return fail("mmu_gemm: the float2 table (colsum) must be 16-B aligned");
+    if (!table && p.colsum && ((uintptr_t)p.colsum & 3)) return fail("mmu_gemm: colsum must be 4-B aligned");
+    if (epi && epi->workspace && off16(epi->workspace))
+      return fail("mmu_gemm: the split-K workspace must be 16-B aligned (float4 slabs)");
+    if ((kind == MMU_EPI_STORE_BNB || kind == MMU_EPI_ADD_RES_BNB) && (off16(p.bn_x) || off16(p.bn_mean)))
+      return fail("mmu_gemm: bn_x and bn_mean must be 16-B aligned");
+  }
   // split-K for long-K / few-tile products (the weight gradients: K = tokens, M x N = a weight matrix)
   p.splitk = 1;
   p.kchunk = K;

@@ -109,7 +109,76 @@ def epilogue(kind=EPI_STORE, bias=None, residual=None, aux=None, colsum=None, dr
                 or res_mask.numel() * 8 != residual.numel():
             raise N.NativeError("epilogue res_mask: contiguous uint8 with numel = residual.numel() / 8")
         e.res_mask = _ptr(res_mask)
+    # the tensors behind the pointers, for gemm's extent checks (a ctypes structure holds no references)
+    e.tensors = dict(bias=bias, residual=residual, aux=aux, colsum=colsum, res_ln=res_ln, bn=bn, res_mask=res_mask)
     return e
+
+
+def _room(t):
+    """bytes from the tensor's data pointer to the end of its storage"""
+    return t.untyped_storage().nbytes() - t.storage_offset() * t.element_size()
+
+
+def _fits(name, t, batch, stride, rows, ld, width):
+    """refuse a call whose last element, (batch - 1) stride + (rows - 1) ld + width elements from
+    the tensor's data pointer, lies outside the tensor's storage"""
+    if t is None:
+        return
+    if stride < 0 or ld < 0:
+        raise N.NativeError(f"gemm {name}: negative stride or leading dimension")
+    need = ((batch - 1) * stride + (rows - 1) * ld + width) * t.element_size()
+    if need > _room(t):
+        raise N.NativeError(f"gemm {name}: the call reaches {need} bytes from the tensor's pointer, its storage "
+                            f"ends after {_room(t)} (batch {batch} stride {stride}, {rows} rows of pitch {ld}, "
+                            f"width {width})")
+
+
+_RES_KINDS = (EPI_BIAS_DROP_RES, EPI_ADD_RES, EPI_ADD_RES_BNB)
+_AUX_KINDS = (EPI_BIAS_GELU, EPI_DGELU, EPI_BIAS_DROP_QGELU)
+_TABLE_KINDS = (EPI_STORE_STATS, EPI_STORE_BNB, EPI_ADD_RES_BNB)
+
+
+def _gemm_extents(A, lda, a_kmajor, B, ldb, b_kmajor, C, ldc, M, N_, K, epi, batch, sA, sB, sC):
+    """plain integer checks of everything mmu_gemm will address (include/mmu.h) against the
+    tensors' storages; they need no device, so they run before the device check"""
+    if min(M, N_, K, batch) <= 0:
+        raise N.NativeError(f"gemm: bad shape M={M} N={N_} K={K} batch={batch}")
+    _fits("A", A, batch, sA, M if a_kmajor else K, lda, K if a_kmajor else M)
+    _fits("B", B, batch, sB, N_ if b_kmajor else K, ldb, K if b_kmajor else N_)
+    _fits("C", C, batch, sC, M, ldc, N_)
+    t = getattr(epi, "tensors", None)
+    if t is None:
+        return
+    kind = epi.kind
+    # (the extents are counted in the tensors' own element sizes: what the kernels read must be that type)
+    for name, dt in (("bias", torch.float32), ("colsum", torch.float32), ("aux", torch.bfloat16)):
+        if t[name] is not None:
+            _want(t[name], dt, f"gemm {name}")
+    if kind not in (EPI_DGELU, EPI_ADD_RES):
+        _fits("bias", t["bias"], batch, epi.bias_bstride, 1, 0, N_)
+    if kind in _RES_KINDS and t["residual"] is not None:
+        r32 = kind == EPI_BIAS_DROP_RES and C.dtype == torch.float32  # the f32 hidden stream
+        _want(t["residual"], torch.float32 if r32 else torch.bfloat16, "gemm residual")
+        _fits("residual", t["residual"], batch, epi.res_bstride, M, epi.ldr, N_)
+    if kind in _AUX_KINDS:
+        _fits("aux", t["aux"], batch, epi.aux_bstride, M, epi.ldx, N_)
+    if kind in _TABLE_KINDS:
+        _fits("colsum (table)", t["colsum"], 1, 0, (M + 63) // 64, 2 * N_, 2 * N_)
+    else:
+        _fits("colsum", t["colsum"], batch, epi.colsum_bstride, 1, 0, N_)
+    if t["res_ln"] is not None:
+        mean, rstd, w, b = t["res_ln"]
+        _fits("res_ln mean", mean, 1, 0, 1, 0, batch * M)
+        _fits("res_ln rstd", rstd, 1, 0, 1, 0, batch * M)
+        _fits("res_ln w", w, batch, epi.res_ln_bstride, 1, 0, N_)
+        _fits("res_ln b", b, batch, epi.res_ln_bstride, 1, 0, N_)
+    if t["bn"] is not None:
+        x, mask, mean = t["bn"]
+        _fits("bn x", x, 1, 0, M, N_, N_)
+        _fits("bn mask", mask, 1, 0, M, N_ // 8, N_ // 8)
+        _fits("bn mean", mean, 1, 0, 1, 0, N_)
+    if t["res_mask"] is not None:
+        _fits("res_mask", t["res_mask"], 1, 0, M, N_ // 8, N_ // 8)
 
 
 def _bnb_check(x, mask, mean, what):
@@ -213,16 +282,18 @@ def gemm(A, lda, a_kmajor, B, ldb, b_kmajor, C, ldc, M, N_, K, epi=None, batch=1
          row_offset=0):
     """C[m,n] = sum_k A(m,k) B(n,k) (+ fused epilogue); see mmu_gemm in include/mmu.h.
     row_step (not None: mmu_gemm_rows) / row_offset: the epilogue's dropout decisions of row m are
-    those of row row_offset + m * row_step of a dense product."""
-    _dev_check(A, B, C)
+    those of row row_offset + m * row_step of a dense product.
+    A call that would address anything outside a tensor's storage is refused (_gemm_extents)."""
     _want(A, torch.bfloat16, "gemm A")
     _want(B, torch.bfloat16, "gemm B")
     cdt = N.MMU_F32 if C.dtype == torch.float32 else N.MMU_BF16
     if C.dtype not in (torch.float32, torch.bfloat16):
         raise N.NativeError("gemm C must be f32 or bf16")
-    # the per-stream f32 scratch serves the split-K weight gradients
     if epi is None:
         epi = epilogue(EPI_STORE)
+    _gemm_extents(A, lda, a_kmajor, B, ldb, b_kmajor, C, ldc, M, N_, K, epi, batch, sA, sB, sC)
+    _dev_check(A, B, C)
+    # the per-stream f32 scratch serves the split-K weight gradients
     if not epi.workspace:  # (on a copy: a caller's epilogue may be reused on another stream)
         epi = type(epi).from_buffer_copy(epi)
         ws = _splitk_workspace(C.device)

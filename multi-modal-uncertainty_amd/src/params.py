@@ -21,6 +21,10 @@ import torch
 STORES = weakref.WeakSet()  # live stores, looked up by the fused optimizer
 
 
+def _up(n, q):
+    return (n + q - 1) // q * q
+
+
 class ParamStore:
     def __init__(self, entries, compute_names):
         """entries: [(name, Parameter)] in flat order (unique params);
@@ -53,11 +57,18 @@ class ParamStore:
     def build(self):
         ps = [self.params[n] for n in self.names]
         device = ps[0].device
-        total = sum(p.numel() for p in ps)
-        flat = torch.empty(total, dtype=torch.float32, device=device)
+        # Every tensor starts on a 16-B boundary (4 floats; 8 elements of the bf16 copies): the kernels
+        # read biases, LayerNorm / BatchNorm vectors and weights as 16-B vectors, and mmu_gemm refuses
+        # a pointer that is not.  A tensor whose size is no multiple of that (a classifier bias) is
+        # followed by zero padding that no view covers; span() still refuses a run across a gap.
+        total = 0
+        for p in ps:  # (the buffer ends with its last tensor: no padding after it)
+            total = _up(total, 4) + p.numel()
+        flat = torch.zeros(total, dtype=torch.float32, device=device)
         grad = torch.zeros(total, dtype=torch.float32, device=device)
         off = 0
         for n, p in zip(self.names, ps):
+            off = _up(off, 4)
             k = p.numel()
             if p.device != device:
                 raise RuntimeError(f"ParamStore: {n} on {p.device}, expected {device}")
@@ -71,10 +82,11 @@ class ParamStore:
             off += k
         self.flat, self.grad = flat, grad
         self._cviews = {}
-        ctot = sum(self.params[n].numel() for n in self.compute_names)
-        self.compute = torch.empty(ctot, dtype=torch.bfloat16, device=device)
+        ctot = sum(_up(self.params[n].numel(), 8) for n in self.compute_names)
+        self.compute = torch.zeros(ctot, dtype=torch.bfloat16, device=device)
         off = 0
         for n in self.compute_names:
+            off = _up(off, 8)
             self.coffsets[n] = off
             off += self.params[n].numel()
         # transposed and flipped copies are re-allocated on the (new) device: a job table

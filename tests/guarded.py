@@ -1,6 +1,6 @@
 """Guarded device buffers for the kernel edge sweeps (test_attention_edges_gpu.py,
 test_layernorm_edges_gpu.py, test_embed_edges_gpu.py, test_batchnorm_edges_gpu.py,
-test_bertadam_edges_gpu.py): every tensor a kernel sees is a view of a
+test_bertadam_edges_gpu.py, test_gemm_edges_gpu.py): every tensor a kernel sees is a view of a
 larger allocation.  Input guards hold NaN, so a read through them poisons the result; outputs are
 pre-filled with a canary, and afterwards everything outside the view must be bit-identical to it.
   out_buf / check_written: NaN-filled contiguous outputs and their check after a launch;
@@ -19,15 +19,33 @@ class Guarded:
     """a [rows, width] view (leading dimension ld) inside a [rows + 2G, ld] allocation, or a
     contiguous n-element view inside n + 2 G1 elements (ld = None)"""
 
-    def __init__(self, dev, dtype, fill, rows, width=None, ld=None):
+    def __init__(self, dev, dtype, fill, rows, width=None, ld=None, guard=None, live=None):
+        """guard: guard rows (2-D) / elements (contiguous) on each side, default G / G1.
+        live: bool mask over the view's rows (2-D) or elements -- what a kernel may write; the rest of
+        the view (the gaps between batch items) is guard like everything outside it"""
         self.ld = ld
         if ld is None:
-            self.alloc = torch.full((rows + 2 * G1,), fill, dtype=dtype, device=dev)
-            self.view = self.alloc[G1:G1 + rows]
+            self.g = G1 if guard is None else guard
+            self.alloc = torch.full((rows + 2 * self.g,), fill, dtype=dtype, device=dev)
+            self.view = self.alloc[self.g:self.g + rows]
         else:
-            self.alloc = torch.full((rows + 2 * G, ld), fill, dtype=dtype, device=dev)
-            self.view = self.alloc[G:G + rows, :width]
+            self.g = G if guard is None else guard
+            self.alloc = torch.full((rows + 2 * self.g, ld), fill, dtype=dtype, device=dev)
+            self.view = self.alloc[self.g:self.g + rows, :width]
+        self.live_mask = None if live is None else live.to(self.alloc.device)
         self.canary = self.alloc.clone()
+
+    def set_canary(self):
+        """the present contents (initial values written through the view) become the canary"""
+        self.canary = self.alloc.clone()
+
+    def unchanged(self):
+        """an input: the whole allocation is bit-identical to the canary (set_canary after the fill)"""
+        return torch.equal(self._bits(self.alloc), self._bits(self.canary))
+
+    def live(self):
+        """the elements a kernel may write (1-D when a live mask is set)"""
+        return self.view if self.live_mask is None else self.view[self.live_mask]
 
     def _bits(self, t):
         return t.view({1: torch.int8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
@@ -38,11 +56,13 @@ class Guarded:
     def guards_intact(self):
         """everything outside the view is bit-identical to the canary"""
         a, c = self._bits(self.alloc).clone(), self._bits(self.canary).clone()
+        g = self.g
         for t in (a, c):
-            if self.ld is None:
-                t[G1:G1 + self.view.shape[0]] = 0
+            v = t[g:g + self.view.shape[0]] if self.ld is None else t[g:g + self.view.shape[0], :self.view.shape[1]]
+            if self.live_mask is None:
+                v.zero_()
             else:
-                t[G:G + self.view.shape[0], :self.view.shape[1]] = 0
+                v[self.live_mask] = 0
         return torch.equal(a, c)
 
 
@@ -64,11 +84,11 @@ def inout_buf(dev, data, fill=NAN):
     return g, g.view.view(data.shape)
 
 
-def out_buf(dev, dtype, *shape, fill=NAN):
+def out_buf(dev, dtype, *shape, fill=NAN, guard=None):
     n = 1
     for s in shape:
         n *= s
-    g = Guarded(dev, dtype, fill, n)
+    g = Guarded(dev, dtype, fill, n, guard=guard)
     return g, g.view.view(*shape)
 
 
@@ -76,7 +96,7 @@ def check_written(bufs, fails, tag):
     for name, g in bufs.items():
         if not g.guards_intact():
             fails.append(f"{tag} {name}: a guard element was written")
-        if not torch.isfinite(g.view.float()).all():
+        if not torch.isfinite(g.live().float()).all():
             fails.append(f"{tag} {name}: live region not finite (unwritten or poisoned)")
 
 

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+from gemm_harness import keep_np as _keep_np  # the restatement of mmu_keep4 / mmu_keep1 (csrc/mmu_common.h)
+
 pytestmark = pytest.mark.gpu
 
 
@@ -201,31 +203,6 @@ def test_gemm_partial_last_wave(dev, Kd):
     f = torch.full((M, N), 0.25, dtype=torch.float32, device=dev)
     k.gemm(A, Kd, True, B, Kd, True, f, N, M, N, Kd, epi=k.epilogue(k.EPI_STORE, accumulate=True))
     close(f[tl], ref[tl] + 0.25)
-
-
-def _keep_np(seed, idx, p):
-    """numpy restatement of mmu_keep4 / mmu_keep1 (csrc/mmu_common.h): the keep decision of
-    element idx of a dropout stream"""
-    import numpy as np
-    M32 = np.uint64(0xFFFFFFFF)
-
-    def lb(x):
-        x = x.astype(np.uint64) & M32
-        x ^= x >> np.uint64(16)
-        x = (x * np.uint64(0x7FEB352D)) & M32
-        x ^= x >> np.uint64(15)
-        x = (x * np.uint64(0x846CA68B)) & M32
-        x ^= x >> np.uint64(16)
-        return x
-    s32 = lb(np.uint64(seed & 0xFFFFFFFF) ^ lb(np.uint64((seed >> 32) ^ 0x68BC21EB)))
-    idx = np.asarray(idx, dtype=np.uint64)
-    quad = idx >> np.uint64(2)
-    x = (((quad << np.uint64(1)) & M32) ^ (((quad >> np.uint64(31)) * np.uint64(0x9E3779B8)) & M32)) ^ s32
-    h0, h1 = lb(x), lb(x ^ np.uint64(1))
-    e = idx & np.uint64(3)
-    draw = np.where(e == 0, h0 & np.uint64(0xFFFF), np.where(e == 1, h0 >> np.uint64(16),
-                    np.where(e == 2, h1 & np.uint64(0xFFFF), h1 >> np.uint64(16))))
-    return draw >= np.uint64(int(p * 65536.0 + 0.5))
 
 
 @pytest.mark.parametrize("M,N", [(256 * 257, 768), (256 * 64 + 32, 3072)])
