@@ -34,8 +34,9 @@ enum { MMU_BF16 = 0, MMU_F32 = 1 };
  * the residual stream's residue pointers inside mmu_batchnorm_fwd / _fwd_sums and the grad_scale
  * argument of mmu_bertadam_step.  3 (round 6): mmu_embed_bwd's workspace size is
  * mmu_embed_bwd_ws_floats().  4 (round 6): mmu_epilogue grows bn_x / bn_mask / bn_mean (the
- * BatchNorm-backward epilogues STORE_BNB / ADD_RES_BNB).  Callers compare mmu_version() with the
- * header they were built against. */
+ * BatchNorm-backward epilogues STORE_BNB / ADD_RES_BNB).  Still 4 with mmu_embed_bwd_ws_floats_h
+ * and H = 1024 in mmu_embed_fwd / _bwd (a new symbol and a newly accepted value; no argument list
+ * changed).  Callers compare mmu_version() with the header they were built against. */
 #define MMU_ABI_VERSION 4
 int mmu_version(void);
 const char* mmu_last_error(void);
@@ -323,8 +324,9 @@ int mmu_seqattn_bwd(const void* QKV, int64_t ld_qkv, const void* O, int64_t ld_o
  * X32 (optional, may be NULL) the same rows in f32 (the encoder's f32 hidden stream);
  * keymask [V*B, Lout] f32 additive; mean/rstd (optional) f32 [V*B*Lout] for backward.
  * Dropout after the LN: drop_img on the image-segment rows (ImageBertEmbeddings.dropout,
- * args.dropout), drop_txt on text rows (BertEmbeddings.dropout 0.1); counter row*768+col.
+ * args.dropout), drop_txt on text rows (BertEmbeddings.dropout 0.1); counter row*H+col.
  * Tables f32: word [vocab,H], pos [maxpos,H], type [2,H]; proj f32 [B, n_img, H].
+ * H is 768 (bert-base) or 1024 (bert-large); any other width is refused.
  */
 int mmu_embed_fwd(const int64_t* ids, const int64_t* seg, const int64_t* txt_mask,
                   const float* proj, const float* word, const float* pos, const float* type,
@@ -336,13 +338,17 @@ int mmu_embed_fwd(const int64_t* ids, const int64_t* seg, const int64_t* txt_mas
 /* Backward of mmu_embed_fwd for the identity variant (training): recomputes the
  * pre-LN sums, LN backward, then scatters: word rows by atomics, position / type
  * / [CLS] / [SEP] by batch reduction, image rows to dproj f32 [B, n_img, H].
- * ws: f32 workspace of at least mmu_embed_bwd_ws_floats(B, T, n_img) floats (ABI 3; ABI 2 took
- * B*S*H + 2*ceil(B*S/64)*H, which is larger for every B > 1).
+ * H is 768 or 1024, as for mmu_embed_fwd.
+ * ws: f32 workspace of at least mmu_embed_bwd_ws_floats_h(B, T, n_img, H) floats;
+ * mmu_embed_bwd_ws_floats(B, T, n_img) is that size at H = 768 (ABI 3; ABI 2 took
+ * B*S*H + 2*ceil(B*S/64)*H, which is larger for every B > 1).  The _h query returns -1 for a
+ * width mmu_embed_bwd refuses.
  * Deterministic mode: the size query returns the larger workspace of that mode (the text rows'
  * f32 gradients [B*T, H], the position partials [ceil(B/16), S, H], the segmented sum's carry
  * rows, the sort's pairs and counters) while the mode is on; the word rows are then summed per
  * id over the tokens in stable sorted order, in chunks of mmu_embed_bwd_det_chunk() tokens. */
 int64_t mmu_embed_bwd_ws_floats(int64_t B, int64_t T, int64_t n_img);
+int64_t mmu_embed_bwd_ws_floats_h(int64_t B, int64_t T, int64_t n_img, int64_t H);
 int64_t mmu_embed_bwd_det_chunk(void);
 int mmu_embed_bwd(const void* dX, const int64_t* ids, const int64_t* seg,
                   const float* proj, const float* word, const float* pos, const float* type,

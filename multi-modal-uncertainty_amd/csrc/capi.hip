@@ -668,7 +668,7 @@ int mmu_embed_fwd(const int64_t* ids, const int64_t* seg, const int64_t* txt_mas
                   int64_t sep_id, const int64_t* idx, int64_t V, int64_t B, int64_t T, int64_t n_img, int64_t Lout,
                   int64_t H, float drop_txt, float drop_img, uint64_t seed, void* X, float* X32, float* keymask,
                   float* mean, float* rstd, mmu_stream_t stream) {
-  if (H != 768) return fail("mmu_embed_fwd: H must be 768");
+  if (H != 768 && H != 1024) return fail("mmu_embed_fwd: H must be 768 or 1024");
   if (!word || !pos || !type || !ln_w || !ln_b || !X || !keymask || !proj) return fail("mmu_embed_fwd: null pointer");
   if (T > 0 && (!ids || !seg)) return fail("mmu_embed_fwd: text ids/segments missing");
   if (V <= 0 || B <= 0 || Lout <= 0 || n_img <= 0) return fail("mmu_embed_fwd: bad shape");
@@ -683,10 +683,13 @@ int mmu_embed_fwd(const int64_t* ids, const int64_t* seg, const int64_t* txt_mas
   return check_launch("mmu_embed_fwd");
 }
 
-int64_t mmu_embed_bwd_ws_floats(int64_t B, int64_t T, int64_t n_img) {
-  const int64_t base = 4 * embed_bwd_blocks(B, n_img + 2 + T) * 768;
-  return deterministic() ? base + embed_bwd_det_ws_floats(B, T, n_img) : base;
+int64_t mmu_embed_bwd_ws_floats_h(int64_t B, int64_t T, int64_t n_img, int64_t H) {
+  if (H != 768 && H != 1024) return -1;
+  const int64_t base = 4 * embed_bwd_blocks(B, n_img + 2 + T) * H;
+  return deterministic() ? base + embed_bwd_det_ws_floats(B, T, n_img, H) : base;
 }
+
+int64_t mmu_embed_bwd_ws_floats(int64_t B, int64_t T, int64_t n_img) { return mmu_embed_bwd_ws_floats_h(B, T, n_img, 768); }
 
 int64_t mmu_embed_bwd_det_chunk(void) { return embed_bwd_det_chunk(); }
 
@@ -696,7 +699,7 @@ int mmu_embed_bwd(const void* dX, const int64_t* ids, const int64_t* seg, const 
                   float drop_img, uint64_t seed, float* d_word,
                   float* d_pos, float* d_type, float* d_ln_w, float* d_ln_b, float* d_proj, float* ws,
                   mmu_stream_t stream) {
-  if (H != 768) return fail("mmu_embed_bwd: H must be 768");
+  if (H != 768 && H != 1024) return fail("mmu_embed_bwd: H must be 768 or 1024");
   if (!dX || !ids || !seg || !proj || !word || !pos || !type || !ln_w || !mean || !rstd || !d_word || !d_pos ||
       !d_type || !d_ln_w || !d_ln_b || !d_proj || !ws)
     return fail("mmu_embed_bwd: null pointer");

@@ -6,7 +6,7 @@
 //   torch.cat             src/mmbt.py:122     (img tokens then text)
 //   encoder_input[:, idx] src/mmbt.py:229     (forward_control gather, one index set per call)
 // and the additive key mask (src/mmbt.py:101-112,203-216) for every output row, so
-// the [B, L, 768] activation is written exactly once, already in its final order.
+// the [B, L, H] activation (H = 768 or 1024) is written exactly once, already in its final order.
 // Also: AdaptiveAvgPool2d((N,1)) of the ResNet map (src/mmbt.py:30,42-44) and the
 // embedding backward (LN backward + word-row atomics + batch reductions).
 #include "mmu_common.h"
@@ -15,22 +15,26 @@
 namespace mmu {
 
 
-static __device__ __forceinline__ void add_row(float (&acc)[3][4], const float* __restrict__ src, int l) {
+// Every row kernel here is templated on NV = H / 256 (3: bert-base, 4: bert-large), as layernorm.hip
+// is: a wave holds a row as float[NV][4], lane l the columns 256 i + 4 l .. + 3.
+template <int NV>
+static __device__ __forceinline__ void add_row(float (&acc)[NV][4], const float* __restrict__ src, int l) {
 #pragma unroll
-  for (int i = 0; i < 3; ++i) {
+  for (int i = 0; i < NV; ++i) {
     float4 a = *(const float4*)(src + 256 * i + 4 * l);
     acc[i][0] += a.x; acc[i][1] += a.y; acc[i][2] += a.z; acc[i][3] += a.w;
   }
 }
 
-// pre-LN embedding sum of source position s for batch row b (H == 768)
-static __device__ __forceinline__ void embed_sum(float (&e)[3][4], const EmbedParams& p, int64_t b, int64_t s,
+// pre-LN embedding sum of source position s for batch row b (H == 256 NV)
+template <int NV>
+static __device__ __forceinline__ void embed_sum(float (&e)[NV][4], const EmbedParams& p, int64_t b, int64_t s,
                                                  int l, float& km) {
 #pragma unroll
-  for (int i = 0; i < 3; ++i)
+  for (int i = 0; i < NV; ++i)
 #pragma unroll
     for (int k = 0; k < 4; ++k) e[i][k] = 0.f;
-  const int64_t H = p.H, nimg = p.n_img;
+  const int64_t H = 256 * NV, nimg = p.n_img;
   km = 0.f;
   if (s <= nimg + 1) {
     if (s == 0) add_row(e, p.word + p.cls_id * H, l);
@@ -48,45 +52,48 @@ static __device__ __forceinline__ void embed_sum(float (&e)[3][4], const EmbedPa
   }
 }
 
+template <int NV>
 __global__ __launch_bounds__(256) void embed_fwd_kernel(EmbedParams p) {
+  constexpr int64_t H = 256 * NV;
   const int l = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int64_t total = p.V * p.B * p.Lout;
   if (row >= total) return;
   const int64_t j = row % p.Lout, vb = row / p.Lout, b = vb % p.B, v = vb / p.B;
   const int64_t s = p.idx ? p.idx[v * p.Lout + j] : j;
-  float e[3][4], km;
-  embed_sum(e, p, b, s, l, km);
+  float e[NV][4], km;
+  embed_sum<NV>(e, p, b, s, l, km);
   float sum = 0.f;
 #pragma unroll
-  for (int i = 0; i < 3; ++i)
+  for (int i = 0; i < NV; ++i)
 #pragma unroll
     for (int k = 0; k < 4; ++k) sum += e[i][k];
-  const float mu = wave_sum(sum) / 768.f;
+  const float mu = wave_sum(sum) / (float)H;
   float q = 0.f;
 #pragma unroll
-  for (int i = 0; i < 3; ++i)
+  for (int i = 0; i < NV; ++i)
 #pragma unroll
     for (int k = 0; k < 4; ++k) { float d = e[i][k] - mu; q += d * d; }
-  const float rs = rsqrtf(wave_sum(q) / 768.f + p.eps);
+  const float rs = rsqrtf(wave_sum(q) / (float)H + p.eps);
   // dropout: ImageBertEmbeddings.dropout (p = args.dropout) on the image-segment rows,
-  // BertEmbeddings.dropout (0.1) on text rows; element counter row*768 + col
+  // BertEmbeddings.dropout (0.1) on text rows; element counter row*H + col (the
+  // stream the GEMM and LayerNorm dropouts index the same way)
   const float dp = s <= p.n_img + 1 ? p.drop_img : p.drop_txt;
   const uint32_t thr = (uint32_t)(dp * 65536.0f + 0.5f);
   const float dsc = dp > 0.f ? 1.0f / (1.0f - dp) : 1.0f;
 #pragma unroll
-  for (int i = 0; i < 3; ++i) {
+  for (int i = 0; i < NV; ++i) {
     const int c = 256 * i + 4 * l;
     float4 w = *(const float4*)(p.ln_w + c), bb = *(const float4*)(p.ln_b + c);
     float y[4] = {(e[i][0] - mu) * rs * w.x + bb.x, (e[i][1] - mu) * rs * w.y + bb.y,
                   (e[i][2] - mu) * rs * w.z + bb.z, (e[i][3] - mu) * rs * w.w + bb.w};
     if (thr) {
-      const uint32_t keep = mmu_keep4(mmu_eff_seed(p.seed, p.seed_off), (uint64_t)(row * 768 + c) >> 2, thr);
+      const uint32_t keep = mmu_keep4(mmu_eff_seed(p.seed, p.seed_off), (uint64_t)(row * H + c) >> 2, thr);
 #pragma unroll
       for (int k = 0; k < 4; ++k) y[k] = ((keep >> k) & 1) ? y[k] * dsc : 0.f;
     }
-    *(bf16x4*)(p.X + row * 768 + c) = bf16x4{f2bf(y[0]), f2bf(y[1]), f2bf(y[2]), f2bf(y[3])};
-    if (p.X32) *(float4*)(p.X32 + row * 768 + c) = make_float4(y[0], y[1], y[2], y[3]);  // the f32 hidden stream
+    *(bf16x4*)(p.X + row * H + c) = bf16x4{f2bf(y[0]), f2bf(y[1]), f2bf(y[2]), f2bf(y[3])};
+    if (p.X32) *(float4*)(p.X32 + row * H + c) = make_float4(y[0], y[1], y[2], y[3]);  // the f32 hidden stream
   }
   if (l == 0) {
     p.keymask[row] = km;
@@ -96,7 +103,9 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(EmbedParams p) {
 
 void embed_fwd_launch(const EmbedParams& p, hipStream_t s) {
   const int64_t total = p.V * p.B * p.Lout;
-  hipLaunchKernelGGL(embed_fwd_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, s, p);
+  const dim3 grid((unsigned)((total + 3) / 4));
+  if (p.H == 1024) hipLaunchKernelGGL(embed_fwd_kernel<4>, grid, dim3(256), 0, s, p);
+  else hipLaunchKernelGGL(embed_fwd_kernel<3>, grid, dim3(256), 0, s, p);
 }
 
 // ---------------------------------------------------------------- backward
@@ -109,15 +118,25 @@ void embed_fwd_launch(const EmbedParams& p, hipStream_t s) {
 // colsum_reduce.  (Round 6: the batch sums used to go through an f32 [B, S, H] copy of the row
 // gradients and a second kernel walking it column-wise: 0.69 ms at B = 256 for 0.4 GB.)
 constexpr int EBW_B = 16;  // samples per block
-// DET (deterministic mode): no atomics.  A text row's dx goes to the scratch dxs [B * T, 768] and
-// the wave's position sum to postab [ceil(B / EBW_B), S, 768], both behind the partial rows in q.ws
+// DET (deterministic mode): no atomics.  A text row's dx goes to the scratch dxs [B * T, H] and
+// the wave's position sum to postab [ceil(B / EBW_B), S, H], both behind the partial rows in q.ws
 // (16 B per lane, whole lines); embed_bwd_launch sums them in a fixed order afterwards.
-template <bool DET>
+// LDS: the four kinds of partial rows are folded two at a time through red[2][4][H], so the block
+// holds 12 H floats with xch instead of 20 H: 36,864 B at H = 768 (61,440 B before), 49,152 B at
+// H = 1024, where the one-shot layout (81,920 B) would pass the 64 KiB static limit.  The sums and
+// their order are the one-shot layout's.
+// Compiler resource usage (-Rpass-analysis=kernel-resource-usage, gfx950), NV = 4:
+//   atomics (DET = false): 49,152 B LDS, 193 VGPRs, 0 B scratch, 2 waves / SIMD;
+//   DET = true (xch unused): 32,768 B LDS, 186 VGPRs, 0 B scratch, 2 waves / SIMD.
+// NV = 3: 36,864 B / 161 VGPRs and 24,576 B / 151 VGPRs, 0 B scratch, 3 waves / SIMD.
+// embed_fwd_kernel<4>: no LDS, 60 VGPRs, 0 B scratch.
+template <int NV, bool DET>
 __global__ __launch_bounds__(256) void embed_bwd_rows_kernel(EmbedBwdParams q, EmbedParams p) {
-  __shared__ float red[4][4][768];                            // aw, ab, type-0, type-1 per wave
-  __shared__ __attribute__((aligned(16))) float xch[4][768];  // per wave: a text row's dx, re-read lane-contiguous
+  constexpr int64_t H = 256 * NV;
+  __shared__ float red[2][4][H];                            // per wave: aw, ab; then type-0, type-1
+  __shared__ __attribute__((aligned(16))) float xch[4][H];  // per wave: a text row's dx, re-read lane-contiguous
   const int l = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int64_t S = q.n_img + 2 + q.T, H = 768;
+  const int64_t S = q.n_img + 2 + q.T;
   const int64_t nblk = (int64_t)gridDim.x * gridDim.y;
   const int64_t blk = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
   float* part = q.ws;
@@ -130,9 +149,9 @@ __global__ __launch_bounds__(256) void embed_bwd_rows_kernel(EmbedBwdParams q, E
   const float dp = s <= q.n_img + 1 ? q.drop_img : q.drop_txt;
   const uint32_t thr = (uint32_t)(dp * 65536.0f + 0.5f);
   const float dsc = dp > 0.f ? 1.0f / (1.0f - dp) : 1.0f;
-  float aw[3][4], ab[3][4], w[3][4], tot[3][4], t1[3][4];
+  float aw[NV][4], ab[NV][4], w[NV][4], tot[NV][4], t1[NV][4];
 #pragma unroll
-  for (int i = 0; i < 3; ++i)
+  for (int i = 0; i < NV; ++i)
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       aw[i][k] = ab[i][k] = tot[i][k] = t1[i][k] = 0.f;
@@ -140,12 +159,12 @@ __global__ __launch_bounds__(256) void embed_bwd_rows_kernel(EmbedBwdParams q, E
     }
   for (int64_t b = b0; live && b < b0 + EBW_B && b < q.B; ++b) {
     const int64_t row = b * S + s;
-    float e[3][4], km;
-    embed_sum(e, p, b, s, l, km);
+    float e[NV][4], km;
+    embed_sum<NV>(e, p, b, s, l, km);
     const float mu = q.mean[row], rs = q.rstd[row];
-    float g[3][4], xh[3][4], s1 = 0.f, s2 = 0.f;
+    float g[NV][4], xh[NV][4], s1 = 0.f, s2 = 0.f;
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
+    for (int i = 0; i < NV; ++i) {
       bf16x4 d = *(const bf16x4*)(q.dX + row * H + 256 * i + 4 * l);
       const uint32_t keep = thr ? mmu_keep4(mmu_eff_seed(q.seed, q.seed_off), (uint64_t)(row * H + 256 * i + 4 * l) >> 2, thr) : 0xFu;
 #pragma unroll
@@ -159,12 +178,12 @@ __global__ __launch_bounds__(256) void embed_bwd_rows_kernel(EmbedBwdParams q, E
         ab[i][k] += dy;
       }
     }
-    s1 = wave_sum(s1) / 768.f;
-    s2 = wave_sum(s2) / 768.f;
+    s1 = wave_sum(s1) / (float)H;
+    s2 = wave_sum(s2) / (float)H;
     const bool seg1 = text && q.seg[b * q.T + (s - q.n_img - 2)] != 0;
     float* wrow = text ? q.d_word + q.ids[b * q.T + (s - q.n_img - 2)] * H : nullptr;
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
+    for (int i = 0; i < NV; ++i) {
       const int c = 256 * i + 4 * l;
       float dx[4];
 #pragma unroll
@@ -187,13 +206,13 @@ __global__ __launch_bounds__(256) void embed_bwd_rows_kernel(EmbedBwdParams q, E
                  // of their rate.  The row sits in this wave's own LDS slice: in-order LDS, no barrier.
       __builtin_amdgcn_wave_barrier();
 #pragma unroll
-      for (int j = 0; j < 12; ++j) atomicAdd(wrow + 64 * j + l, xch[wv][64 * j + l]);
+      for (int j = 0; j < 4 * NV; ++j) atomicAdd(wrow + 64 * j + l, xch[wv][64 * j + l]);
       __builtin_amdgcn_wave_barrier();
     }
   }
   if (live && DET) {  // this position's sum over the block's samples: its row of the block's table slab
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
+    for (int i = 0; i < NV; ++i)
       *(float4*)(postab + ((int64_t)blockIdx.y * S + s) * H + 256 * i + 4 * l) =
           make_float4(tot[i][0], tot[i][1], tot[i][2], tot[i][3]);
   }
@@ -203,31 +222,34 @@ __global__ __launch_bounds__(256) void embed_bwd_rows_kernel(EmbedBwdParams q, E
     float* wr = s == 0 ? q.d_word + q.cls_id * H : (s == q.n_img + 1 ? q.d_word + q.sep_id * H : nullptr);
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
+    for (int i = 0; i < NV; ++i)
       *(float4*)(&xch[wv][256 * i + 4 * l]) = make_float4(tot[i][0], tot[i][1], tot[i][2], tot[i][3]);
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
-    for (int j = 0; j < 12; ++j) {
+    for (int j = 0; j < 4 * NV; ++j) {
       const float v = xch[wv][64 * j + l];
       atomicAdd(q.d_pos + posr * H + 64 * j + l, v);
       if (wr) atomicAdd(wr + 64 * j + l, v);
     }
   }
 #pragma unroll
-  for (int i = 0; i < 3; ++i)
+  for (int half = 0; half < 2; ++half) {  // aw | ab, then type-0 | type-1
+    if (half) __syncthreads();
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int c = 256 * i + 4 * l + k;
-      red[0][wv][c] = aw[i][k];
-      red[1][wv][c] = ab[i][k];
-      red[2][wv][c] = tot[i][k] - t1[i][k];  // token type 0 (every image-segment row, text rows with seg 0)
-      red[3][wv][c] = t1[i][k];
-    }
-  __syncthreads();
-  for (int c = threadIdx.x; c < 768; c += 256)
+    for (int i = 0; i < NV; ++i)
 #pragma unroll
-    for (int r = 0; r < 4; ++r)
-      part[(r * nblk + blk) * H + c] = (red[r][0][c] + red[r][1][c]) + (red[r][2][c] + red[r][3][c]);
+      for (int k = 0; k < 4; ++k) {
+        const int c = 256 * i + 4 * l + k;
+        // token type 0: every image-segment row, text rows with seg 0
+        red[0][wv][c] = half ? tot[i][k] - t1[i][k] : aw[i][k];
+        red[1][wv][c] = half ? t1[i][k] : ab[i][k];
+      }
+    __syncthreads();
+    for (int c = threadIdx.x; c < H; c += 256)
+#pragma unroll
+      for (int r = 0; r < 2; ++r)
+        part[((2 * half + r) * nblk + blk) * H + c] = (red[r][0][c] + red[r][1][c]) + (red[r][2][c] + red[r][3][c]);
+  }
 }
 
 int64_t embed_bwd_blocks(int64_t B, int64_t S) { return ((S + 3) / 4) * ((B + EBW_B - 1) / EBW_B); }
@@ -328,18 +350,20 @@ static __device__ __forceinline__ void st4(float* p, float4 v) {
     p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w;
   }
 }
-static __device__ __forceinline__ void row_rmw(float* __restrict__ dst, const float (&acc)[3][4], int l) {
+template <int NV>
+static __device__ __forceinline__ void row_rmw(float* __restrict__ dst, const float (&acc)[NV][4], int l) {
 #pragma unroll
-  for (int i = 0; i < 3; ++i) {
+  for (int i = 0; i < NV; ++i) {
     float* d = dst + 256 * i + 4 * l;
     float4 o = ld4(d);
     o.x += acc[i][0]; o.y += acc[i][1]; o.z += acc[i][2]; o.w += acc[i][3];
     st4(d, o);
   }
 }
-static __device__ __forceinline__ void row_store(float* __restrict__ dst, const float (&acc)[3][4], int l) {
+template <int NV>
+static __device__ __forceinline__ void row_store(float* __restrict__ dst, const float (&acc)[NV][4], int l) {
 #pragma unroll
-  for (int i = 0; i < 3; ++i)
+  for (int i = 0; i < NV; ++i)
     *(float4*)(dst + 256 * i + 4 * l) = make_float4(acc[i][0], acc[i][1], acc[i][2], acc[i][3]);
 }
 
@@ -348,19 +372,21 @@ static __device__ __forceinline__ void row_store(float* __restrict__ dst, const 
 // wave as its only writer: d_word[id] += sum.  A run that goes on from the previous chunk leaves
 // its sum in carry row 0 of the chunk, one that begins here and goes on into the next chunk in
 // carry row 1; embed_det_carry_kernel folds those.
+template <int NV>
 __global__ __launch_bounds__(64) void embed_det_chunk_kernel(const uint32_t* __restrict__ sk,
                                                              const uint32_t* __restrict__ sv, int64_t n,
                                                              const float* __restrict__ dxs, float* __restrict__ carry,
                                                              float* __restrict__ d_word) {
+  constexpr int64_t H = 256 * NV;
   const int l = threadIdx.x;
   const int64_t c = blockIdx.x, c0 = c * EBW_DET_CHUNK;
   const int cnt = (int)(n - c0 < EBW_DET_CHUNK ? n - c0 : EBW_DET_CHUNK);
   const uint32_t my_k = l < cnt ? sk[c0 + l] : 0u, my_v = l < cnt ? sv[c0 + l] : 0u;
   const bool has_left = c0 > 0, has_right = c0 + cnt < n;
   const uint32_t left_k = has_left ? sk[c0 - 1] : 0u, right_k = has_right ? sk[c0 + cnt] : 0u;
-  float acc[3][4];
+  float acc[NV][4];
 #pragma unroll
-  for (int i = 0; i < 3; ++i)
+  for (int i = 0; i < NV; ++i)
 #pragma unroll
     for (int k = 0; k < 4; ++k) acc[i][k] = 0.f;
   uint32_t cur = __shfl(my_k, 0, 64);
@@ -370,18 +396,18 @@ __global__ __launch_bounds__(64) void embed_det_chunk_kernel(const uint32_t* __r
     if (i == cnt || k != cur) {  // the run of `cur` ends before token i
       const bool left_open = first && has_left && left_k == cur;
       const bool right_open = i == cnt && has_right && right_k == cur;
-      if (left_open) row_store(carry + (2 * c) * 768, acc, l);
-      else if (right_open) row_store(carry + (2 * c + 1) * 768, acc, l);
-      else row_rmw(d_word + (int64_t)cur * 768, acc, l);
+      if (left_open) row_store<NV>(carry + (2 * c) * H, acc, l);
+      else if (right_open) row_store<NV>(carry + (2 * c + 1) * H, acc, l);
+      else row_rmw<NV>(d_word + (int64_t)cur * H, acc, l);
       if (i == cnt) break;
 #pragma unroll
-      for (int a = 0; a < 3; ++a)
+      for (int a = 0; a < NV; ++a)
 #pragma unroll
         for (int b = 0; b < 4; ++b) acc[a][b] = 0.f;
       cur = k;
       first = false;
     }
-    add_row(acc, dxs + (int64_t)__shfl(my_v, i, 64) * 768, l);
+    add_row<NV>(acc, dxs + (int64_t)__shfl(my_v, i, 64) * H, l);
   }
 }
 
@@ -389,9 +415,11 @@ __global__ __launch_bounds__(64) void embed_det_chunk_kernel(const uint32_t* __r
 // columns here, which adds carry row 1 of c and then carry row 0 of every later chunk the run
 // reaches, in chunk order, and d_word[id] += that sum.  The run's end is found by bisection of the
 // sorted keys.
+template <int NV>
 __global__ __launch_bounds__(64) void embed_det_carry_kernel(const uint32_t* __restrict__ sk, int64_t n,
                                                              const float* __restrict__ carry,
                                                              float* __restrict__ d_word) {
+  constexpr int64_t H = 256 * NV;  // gridDim.y == NV
   const int64_t c = blockIdx.x, c0 = c * EBW_DET_CHUNK, c1 = c0 + EBW_DET_CHUNK;
   if (c1 >= n) return;
   const uint32_t id = sk[c1 - 1];
@@ -405,52 +433,54 @@ __global__ __launch_bounds__(64) void embed_det_carry_kernel(const uint32_t* __r
   }
   const int64_t clast = (lo - 1) / EBW_DET_CHUNK;
   const int col = blockIdx.y * 256 + 4 * threadIdx.x;
-  float4 a = *(const float4*)(carry + (2 * c + 1) * 768 + col);
+  float4 a = *(const float4*)(carry + (2 * c + 1) * H + col);
 #pragma unroll 8
   for (int64_t cc = c + 1; cc <= clast; ++cc) {
-    const float4 v = *(const float4*)(carry + (2 * cc) * 768 + col);
+    const float4 v = *(const float4*)(carry + (2 * cc) * H + col);
     a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
   }
-  float* d = d_word + (int64_t)id * 768 + col;
+  float* d = d_word + (int64_t)id * H + col;
   float4 o = ld4(d);
   o.x += a.x; o.y += a.y; o.z += a.z; o.w += a.w;
   st4(d, o);
 }
 
-// Position rows and the [CLS] / [SEP] word rows from postab [nby, S, 768], one writer each, the
+// Position rows and the [CLS] / [SEP] word rows from postab [nby, S, H], one writer each, the
 // nby block rows folded in block order.  Block r < R: d_pos[r] += (the image-segment position r)
 // then (the text position r).  Block R, after every token run of the launches before it:
 // d_word[cls] += position 0's sum, then d_word[sep] += position n_img + 1's (one thread per
 // column does both, so cls == sep stays ordered).
+template <int NV>
 __global__ __launch_bounds__(64) void embed_det_pos_kernel(const float* __restrict__ postab, int64_t nby, int64_t S,
                                                            int64_t T, int64_t n_img, int64_t R, int64_t cls_id,
                                                            int64_t sep_id, float* __restrict__ d_pos,
                                                            float* __restrict__ d_word) {
+  constexpr int64_t H = 256 * NV;  // gridDim.y == NV
   const int col = blockIdx.y * 256 + 4 * threadIdx.x;
   const int64_t r = blockIdx.x;
   auto fold = [&](float* dst, int64_t s) {
     float4 a = ld4(dst + col);
     for (int64_t by = 0; by < nby; ++by) {
-      const float4 v = *(const float4*)(postab + (by * S + s) * 768 + col);
+      const float4 v = *(const float4*)(postab + (by * S + s) * H + col);
       a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
     }
     st4(dst + col, a);
   };
   if (r < R) {
-    if (r <= n_img + 1) fold(d_pos + r * 768, r);
-    if (r < T) fold(d_pos + r * 768, n_img + 2 + r);
+    if (r <= n_img + 1) fold(d_pos + r * H, r);
+    if (r < T) fold(d_pos + r * H, n_img + 2 + r);
   } else {
-    fold(d_word + cls_id * 768, 0);
-    fold(d_word + sep_id * 768, n_img + 1);
+    fold(d_word + cls_id * H, 0);
+    fold(d_word + sep_id * H, n_img + 1);
   }
 }
 
 namespace {
-struct DetLayout {  // offsets in floats behind the [4, nblk, 768] partial rows; every section 16-B aligned
+struct DetLayout {  // offsets in floats behind the [4, nblk, H] partial rows; every section 16-B aligned
   int64_t n, nby, S, nch, ntile, n4;
   int64_t dxs, postab, carry, keys[2], vals[2], counts, total;
 };
-DetLayout det_layout(int64_t B, int64_t T, int64_t n_img) {
+DetLayout det_layout(int64_t B, int64_t T, int64_t n_img, int64_t H) {
   DetLayout d{};
   d.n = B * T;
   d.nby = (B + EBW_B - 1) / EBW_B;
@@ -459,9 +489,9 @@ DetLayout det_layout(int64_t B, int64_t T, int64_t n_img) {
   d.ntile = (d.n + SORT_TILE - 1) / SORT_TILE;
   d.n4 = (d.n + 3) / 4 * 4;
   int64_t o = 0;
-  d.dxs = o; o += d.n * 768;
-  d.postab = o; o += d.nby * d.S * 768;
-  d.carry = o; o += d.nch * 2 * 768;
+  d.dxs = o; o += d.n * H;
+  d.postab = o; o += d.nby * d.S * H;
+  d.carry = o; o += d.nch * 2 * H;
   for (int i = 0; i < 2; ++i) { d.keys[i] = o; o += d.n4; }
   for (int i = 0; i < 2; ++i) { d.vals[i] = o; o += d.n4; }
   d.counts = o; o += 256 * d.ntile;
@@ -470,13 +500,17 @@ DetLayout det_layout(int64_t B, int64_t T, int64_t n_img) {
 }
 }  // namespace
 
-int64_t embed_bwd_det_ws_floats(int64_t B, int64_t T, int64_t n_img) { return det_layout(B, T, n_img).total; }
+int64_t embed_bwd_det_ws_floats(int64_t B, int64_t T, int64_t n_img, int64_t H) {
+  return det_layout(B, T, n_img, H).total;
+}
 int64_t embed_bwd_det_chunk() { return EBW_DET_CHUNK; }
 
+template <int NV>
 static void embed_bwd_det_launch(const EmbedBwdParams& q, const EmbedParams& p, int64_t nblk, hipStream_t s) {
-  const DetLayout d = det_layout(q.B, q.T, q.n_img);
-  float* base = q.ws + 4 * nblk * 768;  // (dxs and postab: the rows kernel derives the same addresses)
-  hipLaunchKernelGGL(embed_bwd_rows_kernel<true>, dim3((unsigned)((p.Lout + 3) / 4), (unsigned)d.nby), dim3(256), 0, s,
+  constexpr int64_t H = 256 * NV;
+  const DetLayout d = det_layout(q.B, q.T, q.n_img, H);
+  float* base = q.ws + 4 * nblk * H;  // (dxs and postab: the rows kernel derives the same addresses)
+  hipLaunchKernelGGL((embed_bwd_rows_kernel<NV, true>), dim3((unsigned)((p.Lout + 3) / 4), (unsigned)d.nby), dim3(256), 0, s,
                      q, p);
   if (d.n > 0) {
     uint32_t* keys[2] = {(uint32_t*)(base + d.keys[0]), (uint32_t*)(base + d.keys[1])};
@@ -499,38 +533,45 @@ static void embed_bwd_det_launch(const EmbedBwdParams& q, const EmbedParams& p, 
         hipLaunchKernelGGL(sort_scatter_kernel<false>, tiles, dim3(64), 0, s, (const int64_t*)nullptr, keys[in],
                            vals[in], keys[out], vals[out], d.n, shift, counts, d.ntile);
     }
-    hipLaunchKernelGGL(embed_det_chunk_kernel, dim3((unsigned)d.nch), dim3(64), 0, s, keys[1], vals[1], d.n,
+    hipLaunchKernelGGL(embed_det_chunk_kernel<NV>, dim3((unsigned)d.nch), dim3(64), 0, s, keys[1], vals[1], d.n,
                        base + d.dxs, base + d.carry, q.d_word);
     if (d.nch > 1)
-      hipLaunchKernelGGL(embed_det_carry_kernel, dim3((unsigned)d.nch, 3), dim3(64), 0, s, keys[1], d.n,
+      hipLaunchKernelGGL(embed_det_carry_kernel<NV>, dim3((unsigned)d.nch, NV), dim3(64), 0, s, keys[1], d.n,
                          base + d.carry, q.d_word);
   }
   const int64_t R = q.n_img + 2 > q.T ? q.n_img + 2 : q.T;
-  hipLaunchKernelGGL(embed_det_pos_kernel, dim3((unsigned)(R + 1), 3), dim3(64), 0, s, base + d.postab, d.nby, d.S,
+  hipLaunchKernelGGL(embed_det_pos_kernel<NV>, dim3((unsigned)(R + 1), NV), dim3(64), 0, s, base + d.postab, d.nby, d.S,
                      q.T, q.n_img, R, q.cls_id, q.sep_id, q.d_pos, q.d_word);
 }
 
-void embed_bwd_launch(const EmbedBwdParams& q, hipStream_t s) {
+template <int NV>
+static void embed_bwd_launch_nv(const EmbedBwdParams& q, hipStream_t s) {
+  constexpr int64_t H = 256 * NV;
   EmbedParams p{};
   p.ids = q.ids; p.seg = q.seg; p.txt_mask = nullptr; p.idx = nullptr;
   p.proj = q.proj; p.word = q.word; p.pos = q.pos; p.type = q.type;
   p.cls_id = q.cls_id; p.sep_id = q.sep_id; p.V = 1; p.B = q.B; p.T = q.T; p.n_img = q.n_img;
-  p.Lout = q.n_img + 2 + q.T; p.H = 768;
+  p.Lout = q.n_img + 2 + q.T; p.H = H;
   const int64_t nblk = embed_bwd_blocks(q.B, p.Lout);
   if (deterministic())
-    embed_bwd_det_launch(q, p, nblk, s);
+    embed_bwd_det_launch<NV>(q, p, nblk, s);
   else
-    hipLaunchKernelGGL(embed_bwd_rows_kernel<false>, dim3((unsigned)((p.Lout + 3) / 4), (unsigned)((q.B + EBW_B - 1) / EBW_B)),
+    hipLaunchKernelGGL((embed_bwd_rows_kernel<NV, false>), dim3((unsigned)((p.Lout + 3) / 4), (unsigned)((q.B + EBW_B - 1) / EBW_B)),
                        dim3(256), 0, s, q, p);
   const float* part = q.ws;
   ColsumJobs jobs{};
-  float* outs[4] = {q.d_ln_w, q.d_ln_b, q.d_type, q.d_type + 768};
+  float* outs[4] = {q.d_ln_w, q.d_ln_b, q.d_type, q.d_type + H};
   for (int z = 0; z < 4; ++z) {
-    jobs.part[z] = part + z * nblk * 768;
+    jobs.part[z] = part + z * nblk * H;
     jobs.parts[z] = nblk;
     jobs.out[z] = outs[z];
   }
-  colsum_reduce_multi_launch(jobs, 4, 768, 1, s);
+  colsum_reduce_multi_launch(jobs, 4, H, 1, s);
+}
+
+void embed_bwd_launch(const EmbedBwdParams& q, hipStream_t s) {
+  if (q.H == 1024) embed_bwd_launch_nv<4>(q, s);
+  else embed_bwd_launch_nv<3>(q, s);
 }
 
 // ---------------------------------------------------------------- AdaptiveAvgPool2d((n,1))

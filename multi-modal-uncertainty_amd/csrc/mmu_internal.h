@@ -175,9 +175,9 @@ struct EmbedBwdParams {
 };
 void embed_bwd_launch(const EmbedBwdParams& p, hipStream_t s);
 int64_t embed_bwd_blocks(int64_t B, int64_t S);
-// deterministic mode: the floats embed_bwd_launch takes behind the [4, nblk, 768] partial rows,
+// deterministic mode: the floats embed_bwd_launch takes behind the [4, nblk, H] partial rows,
 // and the segmented sum's chunk (tokens per wave)
-int64_t embed_bwd_det_ws_floats(int64_t B, int64_t T, int64_t n_img);
+int64_t embed_bwd_det_ws_floats(int64_t B, int64_t T, int64_t n_img, int64_t H);
 int64_t embed_bwd_det_chunk();
 void image_normalize_launch(const uint8_t* in, int64_t n, const float* mean, const float* stdv, void* out,
                             bool out_bf16, hipStream_t s);

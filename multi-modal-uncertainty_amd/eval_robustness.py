@@ -43,6 +43,7 @@ FLAGS = [
     ("--datapath", dict(type=str, default=None)), ("--max_seq_len", dict(type=int, default=512)),
     ("--num_image_embeds", dict(type=int, default=3)), ("--n_workers", dict(type=int, default=0)),
     ("--bert_model", dict(type=str, default="bert-base-uncased")),
+    ("--hidden_sz", dict(type=int, default=768, help="BERT hidden size: 768, or 1024 with bert-large-uncased")),
     ("--gin_file", dict(nargs="*", default=[])), ("--gin_param", dict(nargs="*", default=[])),
     ("--data_dir", dict(type=str, default=None)), ("--sample_size", dict(type=int, default=None)),
     ("--synthetic_images", dict(action="store_true")),
@@ -54,10 +55,16 @@ def get_args(parser):
         parser.add_argument(flag, **kw)
 
 
+def mmbt_model_args(args, n_classes, vocab):
+    """the namespace MultimodalBertClf is built from: the reference's defaults with this run's flags"""
+    from src.testing import make_args
+    return make_args(n_classes=n_classes, vocab=vocab, num_image_embeds=args.num_image_embeds,
+                     bert_model=args.bert_model, hidden_sz=args.hidden_sz)
+
+
 def run_mmbt(args):
     from src import gin
     from src.mmbt import MultimodalBertClf
-    from src.testing import make_args
     from src.training_loop import _load_pretrained_model
     from src.uncertainty import EnsembleMMBT, UncertaintyMeter
     from src.utils import set_seed
@@ -71,8 +78,7 @@ def run_mmbt(args):
     dev = torch.device("cuda:{}".format(args.device))
     members = []
     for i, p in enumerate(paths or [None]):
-        margs = make_args(n_classes=n_classes, vocab=vocab, num_image_embeds=args.num_image_embeds,
-                          bert_model=args.bert_model)
+        margs = mmbt_model_args(args, n_classes, vocab)
         torch.manual_seed(args.seed + i)
         m = MultimodalBertClf(margs)
         if p:

@@ -33,6 +33,7 @@ class Epilogue(ctypes.Structure):
 SIGNATURES = {
     "mmu_version": (c_i32, []),
     "mmu_embed_bwd_ws_floats": (c_i64, [c_i64, c_i64, c_i64]),
+    "mmu_embed_bwd_ws_floats_h": (c_i64, [c_i64, c_i64, c_i64, c_i64]),
     "mmu_last_error": (ctypes.c_char_p, []),
     "mmu_set_seed_offset": (c_i32, [c_vp]),
     "mmu_set_deterministic": (c_i32, [c_i32]),

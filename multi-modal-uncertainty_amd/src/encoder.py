@@ -3,7 +3,7 @@ autograd Function the encoder stacks (replaces pytorch_pretrained_bert BertLayer
 called through ``self.encoder(...)`` at src/mmbt.py:124-126).
 
 Forward per layer (M = B*L token rows, bf16 GEMM operands, f32 accumulation):
-  qkv = X Wqkv^T + bqkv                       mmu_gemm  (fused Q|K|V, [M, 2304])
+  qkv = X Wqkv^T + bqkv                       mmu_gemm  (fused Q|K|V, [M, 3 H])
   O, lse = attention(qkv, keymask)            mmu_attention_fwd (dropout on P)
   S1 = R + dropout(O Wo^T + bo)               mmu_gemm  EPI_BIAS_DROP_RES, f32 residual + f32 out
   A = LN1(S1)                                 mmu_layernorm_fwd_f32 (bf16 operand)
@@ -15,7 +15,7 @@ The hidden state travels as bf16 X (the next GEMM's operand) plus its f32 residu
 embeddings' f32 rows for layer 0, then the previous layer's S2 with its LN statistics (the
 f32 LayerNorm output is recomputed where it is added, never written).  The residual adds
 and LN inputs stay f32, as in the reference's fp32 layer:
-with the stream rounded to bf16 at each of the 48 LN / residual points of 12 layers the
+with the stream rounded to bf16 at each of the 48 LN / residual points of bert-base's 12 layers the
 logits drift by up to 1.6 % of their scale (CPU emulation of the rounding points,
 DESIGN.md §4), with it f32 by 0.5 %.
 Everything behind the attention is row-wise and written once (_rows_forward / _rows_backward):
@@ -24,6 +24,8 @@ layer_forward / layer_backward run it on all M rows, the [CLS]-only last layer
 Backward mirrors it (the gradient stream is bf16); weight gradients are written straight into the flat f32
 gradient buffer (src/params.py) and skipped when the layer is frozen
 (src/framework.py:284-285 toggles requires_grad).
+The width is the weights': every function here reads hidden size, FFN size and head count from
+its LayerWeights (768 / 3072 / 12 for bert-base, 1024 / 4096 / 16 for bert-large; heads of 64).
 """
 
 import os
@@ -32,15 +34,22 @@ import torch
 
 from . import kernels as K
 
-HID, FFN, HEADS = 768, 3072, 12
 bf16 = torch.bfloat16
 
 
 class LayerWeights:
     """Views of one BertLayer's parameters in the ParamStore (f32 masters, bf16 copies, f32 grads)."""
 
-    def __init__(self, store, prefix, layer_module):
+    def __init__(self, store, prefix, layer_module, heads=None):
+        """hid / ffn from the parameter shapes; heads as given, else hid / 64 (the attention
+        kernels' head size)"""
         self.store, self.prefix, self.module = store, prefix, layer_module
+        FFN, HID = store.params[f"{prefix}intermediate.dense.weight"].shape
+        self.hid, self.ffn = int(HID), int(FFN)
+        self.heads = int(heads) if heads is not None else self.hid // 64
+        if self.heads * 64 != self.hid:
+            raise NotImplementedError(f"{prefix}: {self.heads} heads of {self.hid} columns; the attention kernels "
+                                      f"are built for 64-wide heads")
         q = [f"{prefix}attention.self.{n}.weight" for n in ("query", "key", "value")]
         qb = [f"{prefix}attention.self.{n}.bias" for n in ("query", "key", "value")]
         self._names = dict(
@@ -73,11 +82,19 @@ class LayerWeights:
         return self.anchor.requires_grad
 
 
+def _dims(lw):
+    """(hid, ffn, heads) of a layer's weights: the W1 copy's shape, and the head count a
+    LayerWeights carries (any other holder of the same views: 64-wide heads)"""
+    ffn, hid = lw.w116.shape
+    return int(hid), int(ffn), int(getattr(lw, "heads", hid // 64))
+
+
 def _rows_forward(lw, O, R, res_ln, rows, p_hid, seeds, save, row_step=None):
     """The row-wise chain behind the attention, on ``rows`` rows: Wo + dropout + residual, LN1,
     W1 + GELU, W2 + dropout + residual -> (S1, mean1, rstd1, A, Z, Hh, S2).  The dense layer's
     B L rows (row_step None: mmu_gemm), or the last layer's B [CLS] rows with row_step = L, whose
     row b then draws the hidden dropout of the dense layer's row b L."""
+    HID, FFN, _ = _dims(lw)
     dev = O.device
     f32 = torch.float32
     S1 = torch.empty(rows, HID, dtype=f32, device=dev)
@@ -99,13 +116,14 @@ def _rows_forward(lw, O, R, res_ln, rows, p_hid, seeds, save, row_step=None):
 
 
 def layer_forward(lw, X, R, keymask, B, L, p_attn, p_hid, seeds, save, res_ln=None, out32=False):
-    """X bf16 [M, 768] and its f32 residual -> (Y bf16, S2, mean2, rstd2, saved, Y32).
+    """X bf16 [M, H] and its f32 residual -> (Y bf16, S2, mean2, rstd2, saved, Y32).
 
     The f32 residual is ``R`` itself (res_ln None: the embeddings' f32 rows) or the previous
     layer's output LayerNorm recomputed in the GEMM epilogue from its f32 input ``R`` = S2
     and ``res_ln`` = (mean2, rstd2, gamma, beta): the LayerNorms write only their bf16 output
     (the next GEMM operand), never an f32 copy, except Y32 when ``out32`` (the last layer's
     hidden state for the pooler / the encoder API)."""
+    HID, _, HEADS = _dims(lw)
     M = B * L
     dev = X.device
     f32 = torch.float32
@@ -144,7 +162,8 @@ def last_layer_forward(lw, X, R, keymask, B, L, p_attn, p_hid, seeds, save, res_
     src/mmbt.py:124-128): K | V for every row, everything else -- Q, the attention, Wo, LN1, the
     FFN, LN2 -- for the B [CLS] rows only, as compact [B, .] problems whose hidden-dropout
     streams are row-stepped by L, so that row b draws what the dense layer draws in row b L.
-    -> (Y32 [B, 768] f32, saved)."""
+    -> (Y32 [B, H] f32, saved)."""
+    HID, _, HEADS = _dims(lw)
     M = B * L
     dev = X.device
     f32 = torch.float32
@@ -153,7 +172,7 @@ def last_layer_forward(lw, X, R, keymask, B, L, p_attn, p_hid, seeds, save, res_
            epi=K.epilogue(K.EPI_STORE, bias=lw.bqkv[HID:]))
     Xc = _cls_rows(X, B, L)
     K.gemm(Xc, HID, True, lw.wqkv16[:HID], HID, True, qkv, L * 3 * HID, B, HID, HID,
-           epi=K.epilogue(K.EPI_STORE, bias=lw.bqkv[:HID]))  # (row pitch L * 2304: into rows b L)
+           epi=K.epilogue(K.EPI_STORE, bias=lw.bqkv[:HID]))  # (row pitch L * 3 H: into rows b L)
     # (dense-shaped O / lse / keep words: the kernel writes row 0 of each where the dense one does;
     # the other rows are never touched, only the compact copies live on)
     O = torch.empty(M, HID, dtype=bf16, device=dev)
@@ -177,10 +196,11 @@ def last_layer_forward(lw, X, R, keymask, B, L, p_attn, p_hid, seeds, save, res_
 
 
 def last_layer_backward(lw, saved, dY32, keymask, B, L, p_attn, p_hid, seeds, wgrad):
-    """dY32 [B, 768]: the gradient of the [CLS] rows.  The row-wise chain (LN2', W2, gelu', W1,
+    """dY32 [B, H]: the gradient of the [CLS] rows.  The row-wise chain (LN2', W2, gelu', W1,
     LN1', Wo) runs on those B rows; the attention backward has dO in query row 0 only; dX =
     dK|dV . Wk|v for every row, and the [CLS] rows' full dqkv . Wqkv + dS1 on top.  Weight
     gradients: B-row products, but the K | V rows of g_wqkv (the dense product)."""
+    HID, _, HEADS = _dims(lw)
     X, Xc, qkv, Oc, lse0, kw0, S1, mean1, rstd1, A, Z, Hh, S2, mean2, rstd2 = saved
     M = B * L
     dev = dY32.device
@@ -190,7 +210,7 @@ def last_layer_backward(lw, saved, dY32, keymask, B, L, p_attn, p_hid, seeds, wg
     # ---- attention (query row 0) + fused QKV.  The kernel addresses dO / O / lse / the keep
     # words as the dense ones do: dense-shaped buffers with row 0 of each sequence filled in
     dO = torch.empty(M, HID, dtype=bf16, device=dev)
-    K.gemm(dAo, HID, True, lw.wot16, HID, True, dO, L * HID, B, HID, HID)  # (row pitch L * 768: rows b L)
+    K.gemm(dAo, HID, True, lw.wot16, HID, True, dO, L * HID, B, HID, HID)  # (row pitch L * H: rows b L)
     O = torch.empty(M, HID, dtype=bf16, device=dev)
     O.view(B, L, HID)[:, 0] = Oc
     lse = torch.empty(B * HEADS, L, dtype=torch.float32, device=dev)
@@ -202,7 +222,7 @@ def last_layer_backward(lw, saved, dY32, keymask, B, L, p_attn, p_hid, seeds, wg
     dqkv = torch.empty(M, 3 * HID, dtype=bf16, device=dev)  # dQ columns: the [CLS] rows only
     dbs = K.attention_row0_dbias(B, HEADS, dev) if wgrad else None
     K.attention_row0_bwd(qkv, keymask, O, dO, lse, dqkv, B, L, HEADS, p_attn, dmask, dbs)
-    dqkv_c = _cls_rows(dqkv, B, L)  # [B, 2304]: the full dQ | dK | dV rows of the [CLS] tokens
+    dqkv_c = _cls_rows(dqkv, B, L)  # [B, 3 H]: the full dQ | dK | dV rows of the [CLS] tokens
     if wgrad:
         acc = K.epilogue(K.EPI_STORE, accumulate=True)
 
@@ -214,7 +234,7 @@ def last_layer_backward(lw, saved, dY32, keymask, B, L, p_attn, p_hid, seeds, wg
         side.run(wqkv, dqkv, dqkv_c, X, Xc, dbs)
     dX = torch.empty(M, HID, dtype=bf16, device=dev)
     K.gemm(dqkv[:, HID:], 3 * HID, True, lw.wqkvt16[:, HID:], 3 * HID, True, dX, HID, M, HID, 2 * HID)
-    # the [CLS] rows again, whole: dqkv . Wqkv + dS1 as the dense layer forms them (row pitch L * 768)
+    # the [CLS] rows again, whole: dqkv . Wqkv + dS1 as the dense layer forms them (row pitch L * H)
     K.gemm(dqkv_c, 3 * HID, True, lw.wqkvt16, 3 * HID, True, dX, L * HID, B, HID, 3 * HID,
            epi=K.epilogue(K.EPI_ADD_RES, residual=dS1))
     return dX, side
@@ -224,8 +244,8 @@ def encoder_stack(lws, X, X32, keymask, B, L, p_attn, p_hid, seeds_of, need_grad
                   cls_only=False):
     """Run the fused layers over (X bf16, X32 f32 embedding rows); returns the f32 hidden
     state of the last layer, or of every layer (all_layers); with cls_only only the last layer's
-    [CLS] rows [B, 768] (the pooler's input: no f32 copy of the other B (L - 1) rows, and no
-    [B L, 768] f32 zero gradient for them in the backward; with LAST_LAYER_CLS that layer computes
+    [CLS] rows [B, H] (the pooler's input: no f32 copy of the other B (L - 1) rows, and no
+    [B L, H] f32 zero gradient for them in the backward; with LAST_LAYER_CLS that layer computes
     nothing else)."""
     R, rln, outs = X32, None, []
     n = len(lws)
@@ -369,6 +389,7 @@ def _rows_backward(lw, side, dY, S2, mean2, rstd2, Hh, Z, A, S1, mean1, rstd1, O
     LN2', W2, gelu', W1, LN1' and the weight gradients of W2, W1, Wo (``O``: Wo's operand) with
     their bias / LayerNorm column sums, handed to ``side`` -> (dS1, dAo), the gradients of the
     residual stream at the attention output and of O Wo^T + bo."""
+    HID, FFN, _ = _dims(lw)
     dev = dY.device
     P = K.ln_parts(rows)
     pw = pb = pbias = pw1 = pb1 = pbias1 = None
@@ -406,6 +427,7 @@ def _rows_backward(lw, side, dY, S2, mean2, rstd2, Hh, Z, A, S1, mean1, rstd1, O
 
 def layer_backward(lw, saved, dY, keymask, B, L, p_attn, p_hid, seeds, wgrad):
     X, qkv, O, lse, dmask, S1, mean1, rstd1, A, Z, Hh, S2, mean2, rstd2 = saved
+    HID, _, HEADS = _dims(lw)
     M = B * L
     dev = dY.device
     side = _Side(dev, wgrad)
@@ -474,7 +496,7 @@ def _after_backward(lw, side, wgrad, hook, flush):
 
 
 class BertLayerFunction(torch.autograd.Function):
-    """One fused BertLayer: X bf16 [B*L, 768] + its f32 residual (R, res_ln: see
+    """One fused BertLayer: X bf16 [B*L, H] + its f32 residual (R, res_ln: see
     layer_forward) -> (Y, S2, mean2, rstd2, Y32).  S2 / mean2 / rstd2 (the next layer's
     residual source) are non-differentiable; the layer's whole input gradient is returned
     for X.  The output gradient arrives on Y from the next layer or on Y32 (out32: the last
@@ -502,6 +524,7 @@ class BertLayerFunction(torch.autograd.Function):
     def backward(ctx, dY, _dS2, _dmean2, _drstd2, dY32):
         lw, keymask, B, L, p_attn, p_hid, seeds, hook, flush = ctx.meta
         wgrad = lw.trainable()
+        HID = _dims(lw)[0]
         if dY32 is not None and dY32.numel():
             if dY32.shape[0] == B and B * L != B:  # out32 "cls": the gradient of the [CLS] rows only
                 g = torch.zeros(B * L, HID, dtype=bf16, device=dY32.device) if dY is None else dY.clone()
@@ -521,8 +544,8 @@ class BertLayerFunction(torch.autograd.Function):
 
 
 class BertLastLayerFunction(torch.autograd.Function):
-    """The last fused BertLayer of a [CLS]-pooled stack (LAST_LAYER_CLS): X bf16 [B*L, 768] + its
-    f32 residual -> the [CLS] rows' f32 output [B, 768] (last_layer_forward); the layer's whole
+    """The last fused BertLayer of a [CLS]-pooled stack (LAST_LAYER_CLS): X bf16 [B*L, H] + its
+    f32 residual -> the [CLS] rows' f32 output [B, H] (last_layer_forward); the layer's whole
     input gradient is returned for X, as in BertLayerFunction."""
 
     @staticmethod

@@ -589,38 +589,57 @@ def seqattn_bwd(qkv, O, dO, lse2, delta, dqkv, S, N_, heads):
            _ptr(delta), _ptr(dqkv), dqkv.stride(0), S, N_, heads, D, _stream(qkv))
 
 
+EMBED_WIDTHS = (768, 1024)  # the widths embed.hip instantiates (bert-base, bert-large)
+
+
+def embed_bwd_ws_floats(B, T, n_img, H=768):
+    """f32 elements of embed_bwd's workspace at width H, in the mode that is on now"""
+    n = N.load().mmu_embed_bwd_ws_floats_h(int(B), int(T), int(n_img), int(H))
+    if n < 0:
+        raise N.NativeError(f"embed_bwd: H must be 768 or 1024, got {H}")
+    return n
+
+
 def _embed_common(who, ids, seg, proj, word, pos, typ, ln_w, cls_id, sep_id, B, T, n_img):
     """Host-side argument checks shared by embed_fwd / embed_bwd (shapes and dtypes only; the
-    values of ids / seg / idx are not read)"""
+    values of ids / seg / idx are not read).  Returns H, the width of the word table (768 or 1024),
+    which every other tensor is held to."""
     B, T, n_img = int(B), int(T), int(n_img)
     for name, t in (("ids", ids), ("seg", seg)):
         _want(t, torch.int64, f"{who} {name}")
         if tuple(t.shape) != (B, T) or not t.is_contiguous():
             raise N.NativeError(f"{who}: {name} must be contiguous int64 [B, T] = [{B}, {T}], got {tuple(t.shape)}")
     _want(proj, torch.float32, f"{who} proj")
-    if tuple(proj.shape) != (B, n_img, 768) or not proj.is_contiguous():
-        raise N.NativeError(f"{who}: proj must be contiguous f32 [B, n_img, 768] = [{B}, {n_img}, 768], got "
+    # the word table sets the width: an unknown one is named before anything else is held to it
+    if word.dim() == 2 and word.shape[1] not in EMBED_WIDTHS:
+        _want(word, torch.float32, f"{who} word")
+        raise N.NativeError(f"{who}: word must be a contiguous f32 [n, 768] or [n, 1024] table (the widths the "
+                            f"embedding kernels are built for), got {tuple(word.shape)}")
+    H = word.shape[1] if word.dim() == 2 else 768
+    if tuple(proj.shape) != (B, n_img, H) or not proj.is_contiguous():
+        raise N.NativeError(f"{who}: proj must be contiguous f32 [B, n_img, {H}] = [{B}, {n_img}, {H}], got "
                             f"{tuple(proj.shape)}")
     for name, t in (("word", word), ("pos", pos), ("typ", typ)):
         _want(t, torch.float32, f"{who} {name}")
-        if t.dim() != 2 or t.shape[1] != 768 or not t.is_contiguous():
-            raise N.NativeError(f"{who}: {name} must be a contiguous f32 [n, 768] table, got {tuple(t.shape)}")
+        if t.dim() != 2 or t.shape[1] != H or not t.is_contiguous():
+            raise N.NativeError(f"{who}: {name} must be a contiguous f32 [n, {H}] table, got {tuple(t.shape)}")
     _want(ln_w, torch.float32, f"{who} ln_w")
-    if ln_w.numel() != 768 or not ln_w.is_contiguous():
-        raise N.NativeError(f"{who}: ln_w must hold 768 contiguous elements, got {ln_w.numel()}")
+    if ln_w.numel() != H or not ln_w.is_contiguous():
+        raise N.NativeError(f"{who}: ln_w must hold {H} contiguous elements, got {ln_w.numel()}")
     if max(n_img + 2, T) > pos.shape[0]:
         raise N.NativeError(f"{who}: max(n_img + 2, T) = {max(n_img + 2, T)} exceeds the {pos.shape[0]} position rows")
     if not (0 <= int(cls_id) < word.shape[0] and 0 <= int(sep_id) < word.shape[0]):
         raise N.NativeError(f"{who}: cls_id / sep_id = {cls_id} / {sep_id} outside the {word.shape[0]} word rows")
     if typ.shape[0] < 2:
         raise N.NativeError(f"{who}: typ must hold >= 2 token-type rows, got {typ.shape[0]}")
+    return H
 
 
 def embed_fwd(ids, seg, txt_mask, proj, word, pos, typ, ln_w, ln_b, eps, cls_id, sep_id, idx, V, B, T, n_img, Lout,
               X, keymask, mean=None, rstd=None, drop_txt=0.0, drop_img=0.0, seed=0, X32=None):
     """X32 (optional, f32 like X): the same rows in f32, the encoder's f32 hidden stream."""
     who = "embed_fwd"
-    _embed_common(who, ids, seg, proj, word, pos, typ, ln_w, cls_id, sep_id, B, T, n_img)
+    H = _embed_common(who, ids, seg, proj, word, pos, typ, ln_w, cls_id, sep_id, B, T, n_img)
     rows = int(V) * int(B) * int(Lout)
     if txt_mask is not None:
         _want(txt_mask, torch.int64, f"{who} txt_mask")
@@ -628,8 +647,8 @@ def embed_fwd(ids, seg, txt_mask, proj, word, pos, typ, ln_w, ln_b, eps, cls_id,
             raise N.NativeError(f"{who}: txt_mask must be contiguous int64 [B, T] = [{B}, {T}], got "
                                 f"{tuple(txt_mask.shape)}")
     _want(ln_b, torch.float32, f"{who} ln_b")
-    if ln_b.numel() != 768 or not ln_b.is_contiguous():
-        raise N.NativeError(f"{who}: ln_b must hold 768 contiguous elements, got {ln_b.numel()}")
+    if ln_b.numel() != H or not ln_b.is_contiguous():
+        raise N.NativeError(f"{who}: ln_b must hold {H} contiguous elements, got {ln_b.numel()}")
     if idx is not None:
         _want(idx, torch.int64, f"{who} idx")
         if tuple(idx.shape) != (V, Lout) or not idx.is_contiguous():
@@ -639,8 +658,8 @@ def embed_fwd(ids, seg, txt_mask, proj, word, pos, typ, ln_w, ln_b, eps, cls_id,
         if t is None:
             continue
         _want(t, dt, f"{who} {name}")
-        if tuple(t.shape) != (rows, 768) or not t.is_contiguous():
-            raise N.NativeError(f"{who}: {name} must be contiguous [V * B * Lout, 768] = [{rows}, 768], got "
+        if tuple(t.shape) != (rows, H) or not t.is_contiguous():
+            raise N.NativeError(f"{who}: {name} must be contiguous [V * B * Lout, {H}] = [{rows}, {H}], got "
                                 f"{tuple(t.shape)}")
     for name, t in (("keymask", keymask), ("mean", mean), ("rstd", rstd)):
         if t is None:
@@ -651,7 +670,7 @@ def embed_fwd(ids, seg, txt_mask, proj, word, pos, typ, ln_w, ln_b, eps, cls_id,
                                 f"{t.numel()}")
     _dev_check(ids, seg, txt_mask, idx, proj, word, pos, typ, ln_w, ln_b, X, X32, keymask, mean, rstd)
     N.call("mmu_embed_fwd", _ptr(ids), _ptr(seg), _ptr(txt_mask), _ptr(proj), _ptr(word), _ptr(pos), _ptr(typ),
-           _ptr(ln_w), _ptr(ln_b), float(eps), int(cls_id), int(sep_id), _ptr(idx), V, B, T, n_img, Lout, 768,
+           _ptr(ln_w), _ptr(ln_b), float(eps), int(cls_id), int(sep_id), _ptr(idx), V, B, T, n_img, Lout, H,
            float(drop_txt), float(drop_img), int(seed), _ptr(X), _ptr(X32), _ptr(keymask), _ptr(mean), _ptr(rstd),
            _stream(X))
 
@@ -659,11 +678,11 @@ def embed_fwd(ids, seg, txt_mask, proj, word, pos, typ, ln_w, ln_b, eps, cls_id,
 def embed_bwd(dX, ids, seg, proj, word, pos, typ, ln_w, mean, rstd, cls_id, sep_id, B, T, n_img, d_word, d_pos,
               d_type, d_ln_w, d_ln_b, d_proj, drop_txt=0.0, drop_img=0.0, seed=0):
     who = "embed_bwd"
-    _embed_common(who, ids, seg, proj, word, pos, typ, ln_w, cls_id, sep_id, B, T, n_img)
+    H = _embed_common(who, ids, seg, proj, word, pos, typ, ln_w, cls_id, sep_id, B, T, n_img)
     rows = int(B) * (int(n_img) + 2 + int(T))
     _want(dX, torch.bfloat16, f"{who} dX")
-    if tuple(dX.shape) != (rows, 768) or not dX.is_contiguous():
-        raise N.NativeError(f"{who}: dX must be contiguous bf16 [B * (n_img + 2 + T), 768] = [{rows}, 768], got "
+    if tuple(dX.shape) != (rows, H) or not dX.is_contiguous():
+        raise N.NativeError(f"{who}: dX must be contiguous bf16 [B * (n_img + 2 + T), {H}] = [{rows}, {H}], got "
                             f"{tuple(dX.shape)}")
     for name, t in (("mean", mean), ("rstd", rstd)):
         _want(t, torch.float32, f"{who} {name}")
@@ -676,9 +695,9 @@ def embed_bwd(dX, ids, seg, proj, word, pos, typ, ln_w, mean, rstd, cls_id, sep_
             raise N.NativeError(f"{who}: {name} must be contiguous f32 {tuple(like.shape)} like its parameter, got "
                                 f"{tuple(t.shape)}")
     _dev_check(dX, ids, seg, proj, word, pos, typ, ln_w, mean, rstd, d_word, d_pos, d_type, d_ln_w, d_ln_b, d_proj)
-    ws = torch.empty(N.load().mmu_embed_bwd_ws_floats(B, T, n_img), dtype=torch.float32, device=dX.device)
+    ws = torch.empty(embed_bwd_ws_floats(B, T, n_img, H), dtype=torch.float32, device=dX.device)
     N.call("mmu_embed_bwd", _ptr(dX), _ptr(ids), _ptr(seg), _ptr(proj), _ptr(word), _ptr(pos), _ptr(typ),
-           _ptr(ln_w), _ptr(mean), _ptr(rstd), int(cls_id), int(sep_id), B, T, n_img, 768, float(drop_txt),
+           _ptr(ln_w), _ptr(mean), _ptr(rstd), int(cls_id), int(sep_id), B, T, n_img, H, float(drop_txt),
            float(drop_img), int(seed), _ptr(d_word),
            _ptr(d_pos), _ptr(d_type), _ptr(d_ln_w), _ptr(d_ln_b), _ptr(d_proj), _ptr(ws), _stream(dX))
 

@@ -1,9 +1,9 @@
-"""MMBT (BERT-base + ResNet-152) on the MI355X HIP kernels -- drop-in for the
+"""MMBT (BERT-base or BERT-large + ResNet-152) on the MI355X HIP kernels -- drop-in for the
 reference ``src/mmbt.py`` (classes, methods, argument order, state_dict keys).
 
 Reference API kept (src/mmbt.py:15-262):
   ImageEncoder(args)                 .forward(img) -> [B, N, 2048]
-  ImageBertEmbeddings(args, emb)     .forward(feats, token_type_ids) -> [B, N+2, 768]
+  ImageBertEmbeddings(args, emb)     .forward(feats, token_type_ids) -> [B, N+2, H]
   MultimodalBertEncoder(args)        .forward / forward_img_only / forward_txt_only / forward_control
   MultimodalBertClf(args)            same + .compute_loss(y_hat, y, eval=False)
   sub-modules enc.txt_embeddings, enc.img_embeddings, enc.img_encoder, enc.encoder, enc.pooler, clf
@@ -11,10 +11,12 @@ Reference API kept (src/mmbt.py:15-262):
 What runs where on the GPU:
   ResNet-152 trunk      MIOpen (PyTorch-ROCm), bf16 autocast, channels-last
   row pooling           mmu_row_pool_fwd/bwd           (AdaptiveAvgPool2d((N,1)) + transpose)
-  image projection      torch f32 linear (2048->768, 3 rows per sample)
+  image projection      torch f32 linear (2048->H, 3 rows per sample)
   token embed + concat  mmu_embed_fwd/bwd             (one pass; variants = index gather)
-  12 BERT layers        src/encoder.py                 (MFMA GEMMs + flash attention + LN)
-  pooler + classifier   torch f32 (768x768, 768x101 on one row per sample)
+  12 / 24 BERT layers   src/encoder.py                 (MFMA GEMMs + flash attention + LN)
+  pooler + classifier   torch f32 (HxH, Hx101 on one row per sample)
+H = 768 (bert-base-uncased) or 1024 (bert-large-uncased): the layers read their width from the
+weights, the embedding kernels are instantiated for both.
 No CPU fallback: the encoder path raises on CPU tensors.
 """
 import torch
@@ -29,6 +31,7 @@ from .resnet import StoreConv2d, resnet152_trunk
 BERT_CONFIGS = {
     # name: (layers, hidden, heads, intermediate, vocab, max_pos, type_vocab)
     "bert-base-uncased": (12, 768, 12, 3072, 30522, 512, 2),
+    "bert-large-uncased": (24, 1024, 16, 4096, 30522, 512, 2),
 }
 HIDDEN_DROPOUT = 0.1     # bert-base-uncased hidden_dropout_prob
 ATTN_DROPOUT = 0.1       # bert-base-uncased attention_probs_dropout_prob
@@ -38,12 +41,14 @@ LN_EPS = 1e-12
 def _bert_shape(args):
     name = getattr(args, "bert_model", "bert-base-uncased")
     if name not in BERT_CONFIGS:
-        raise NotImplementedError(f"{name}: the HIP path is built for bert-base (768 hidden, 12 x 64 heads)")
+        raise NotImplementedError(f"{name}: the HIP path is built for {' and '.join(BERT_CONFIGS)} "
+                                  f"(768 or 1024 hidden, 64-wide heads)")
     layers, hid, heads, inter, vocab, max_pos, tv = BERT_CONFIGS[name]
     layers = getattr(args, "bert_layers", layers)
     vocab = getattr(args, "vocab_size", vocab)
     if getattr(args, "hidden_sz", hid) != hid:
-        raise NotImplementedError("hidden_sz must be 768 for bert-base")
+        # (the reference builds clf = Linear(hidden_sz, n_classes) and crashes there)
+        raise NotImplementedError(f"hidden_sz must be {hid} for {name}, got {args.hidden_sz}: pass --hidden_sz {hid}")
     return layers, hid, heads, inter, vocab, max_pos, tv
 
 
@@ -77,7 +82,7 @@ class BertEmbeddings(nn.Module):
         self._owner = None
 
     def forward(self, input_ids, token_type_ids=None):
-        """Text-only embedding [B, T, 768] (inference helper; training uses the fused model path)."""
+        """Text-only embedding [B, T, H] (inference helper; training uses the fused model path)."""
         return self._owner._text_embeddings(input_ids, token_type_ids)
 
 
@@ -136,7 +141,7 @@ class BertEncoder(nn.Module):
         self._owner = None
 
     def forward(self, hidden_states, attention_mask, output_all_encoded_layers=True):
-        """0.6.x call contract: hidden [B,L,768], additive mask [B,1,1,L] -> list of [B,L,768]."""
+        """0.6.x call contract: hidden [B,L,H], additive mask [B,1,1,L] -> list of [B,L,H]."""
         return self._owner._run_encoder_api(hidden_states, attention_mask, output_all_encoded_layers)
 
 
@@ -194,8 +199,9 @@ class EmbedFunction(torch.autograd.Function):
         n = proj.shape[1]
         L = n + 2 + T
         dev = proj.device
-        X = torch.empty(B * L, 768, dtype=torch.bfloat16, device=dev)
-        X32 = torch.empty(B * L, 768, dtype=torch.float32, device=dev)
+        H = proj.shape[2]
+        X = torch.empty(B * L, H, dtype=torch.bfloat16, device=dev)
+        X32 = torch.empty(B * L, H, dtype=torch.float32, device=dev)
         km = torch.empty(B, L, dtype=torch.float32, device=dev)
         mean = torch.empty(B * L, dtype=torch.float32, device=dev)
         rstd = torch.empty(B * L, dtype=torch.float32, device=dev)
@@ -229,7 +235,7 @@ class EmbedFunction(torch.autograd.Function):
 
 
 class ProjectFunction(torch.autograd.Function):
-    """img_embeddings Linear(2048 -> 768) on the pooled features (reference src/mmbt.py:61,70).
+    """img_embeddings Linear(2048 -> H) on the pooled features (reference src/mmbt.py:61,70).
     Its backward accumulates dW / db straight into the flat gradient store and only then
     reports the "proj" gradient segment done (src/dp.py), so the segment's all-reduce is
     ordered after the accumulation on the compute stream (an AccumulateGrad node of
@@ -318,7 +324,7 @@ class ImageBertEmbeddings(nn.Module):
         return F.linear(feats.float(), w, b)
 
     def forward(self, input_imgs, token_type_ids=None):
-        """[B,N,2048] -> [B,N+2,768] (reference forward, src/mmbt.py:58-83)."""
+        """[B,N,2048] -> [B,N+2,H] (reference forward, src/mmbt.py:58-83)."""
         return self._owner._image_embeddings(self.project(input_imgs))
 
 
@@ -332,6 +338,7 @@ class MultimodalBertEncoder(nn.Module):
         self.img_embeddings = ImageBertEmbeddings(args, self.txt_embeddings)
         self.img_encoder = ImageEncoder(args)
         self.encoder = BertEncoder(layers, hid, inter)
+        self.hid, self.heads = hid, heads
         self.pooler = BertPooler(hid)
         init_bert_weights(self.txt_embeddings)
         init_bert_weights(self.encoder)
@@ -384,7 +391,7 @@ class MultimodalBertEncoder(nn.Module):
 
     def _attach_store(self, store, prefix):
         self._store, self._prefix = store, prefix
-        self._lw = [LayerWeights(store, f"{prefix}encoder.layer.{i}.", lyr) for i, lyr in enumerate(self.encoder.layer)]
+        self._lw = [LayerWeights(store, f"{prefix}encoder.layer.{i}.", lyr, self.heads) for i, lyr in enumerate(self.encoder.layer)]
         for name, m in self.img_encoder.named_modules(prefix=f"{prefix}img_encoder"):
             if isinstance(m, StoreConv2d) and f"{name}.weight" in store.coffsets:
                 m.attach_compute(store, f"{name}.weight")
@@ -433,8 +440,8 @@ class MultimodalBertEncoder(nn.Module):
         L = self.n_img + 2 + T if idx is None else Lout
         if idx is not None:
             idx = idx.reshape(V, L)  # (the variant forwards pass one 1-D index set)
-        X = torch.empty(V * B * L, 768, dtype=torch.bfloat16, device=dev)
-        X32 = torch.empty(V * B * L, 768, dtype=torch.float32, device=dev)
+        X = torch.empty(V * B * L, self.hid, dtype=torch.bfloat16, device=dev)
+        X32 = torch.empty(V * B * L, self.hid, dtype=torch.float32, device=dev)
         km = torch.empty(V * B, L, dtype=torch.float32, device=dev)
         e = self.txt_embeddings
         K.embed_fwd(txt, segment, txt_mask, proj.contiguous(), e.word_embeddings.weight, e.position_embeddings.weight,
@@ -444,7 +451,7 @@ class MultimodalBertEncoder(nn.Module):
         return (X, X32), km, L
 
     def _encode(self, XX, km, nb, L):
-        """(X bf16, X32 f32) [nb*L, 768], km [nb, L] -> the last layer's [CLS] rows [nb, 768] f32
+        """(X bf16, X32 f32) [nb*L, H], km [nb, L] -> the last layer's [CLS] rows [nb, H] f32
         (all the pooler reads of the f32 hidden stream; see src/encoder.py)."""
         X, X32 = XX
         act = self._dropout_active()
@@ -456,9 +463,9 @@ class MultimodalBertEncoder(nn.Module):
                              need_grad, self._grad_ready_hook, cls_only=True)
 
     def _pool(self, X, nb, L):
-        """the pooler on the [CLS] rows: X is the last layer's [nb, 768] [CLS] rows (_encode) or
-        its whole [nb * L, 768] output"""
-        return self.pooler(X.view(nb, L, 768) if X.shape[0] != nb or L == 1 else X.view(nb, 1, 768))
+        """the pooler on the [CLS] rows: X is the last layer's [nb, H] [CLS] rows (_encode) or
+        its whole [nb * L, H] output"""
+        return self.pooler(X.view(nb, L, self.hid) if X.shape[0] != nb or L == 1 else X.view(nb, 1, self.hid))
 
     # ---------------------------------------------------------------- reference forwards
     def forward(self, input_txt, attention_mask, segment, input_img):
@@ -519,16 +526,16 @@ class MultimodalBertEncoder(nn.Module):
         dummy = torch.zeros(B, 0, dtype=torch.long, device=proj.device)
         (_, X32), _, L = self._embed(dummy, dummy, dummy, proj, idx=torch.arange(self.n_img + 2, device=proj.device),
                                      Lout=self.n_img + 2)
-        return X32.view(B, L, 768)
+        return X32.view(B, L, self.hid)
 
     def _text_embeddings(self, ids, token_type_ids=None):
         self._prepare()
         B, T = ids.shape
         seg = torch.zeros_like(ids) if token_type_ids is None else token_type_ids
-        proj = torch.zeros(B, self.n_img, 768, device=ids.device)
+        proj = torch.zeros(B, self.n_img, self.hid, device=ids.device)
         idx = torch.arange(T, device=ids.device) + self.n_img + 2
         (_, X32), _, L = self._embed(ids, torch.ones_like(ids), seg, proj, idx=idx, Lout=T)
-        return X32.view(B, T, 768)
+        return X32.view(B, T, self.hid)
 
 
 def control_indices(total_embeds, num_embeds):

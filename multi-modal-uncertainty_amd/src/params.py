@@ -6,7 +6,7 @@ finishes them (classifier, pooler, encoder layers 11..0, embeddings, ResNet
 layer4..stem).  This gives:
   * the fused BertAdam one launch over all 169 M parameters (src/optim.py);
   * contiguous reverse-layer gradient buckets for the RCCL all-reduce (src/dp.py);
-  * fused views (Q|K|V weight [2304,768], bias [2304]) the kernels read directly;
+  * fused views (Q|K|V weight [3H,H], bias [3H]; H = 768 or 1024) the kernels read directly;
   * bf16 copies of every GEMM weight, written by the optimizer kernel, resynced
     only when the f32 masters were changed elsewhere (load_state_dict, .to());
   * transposed (K-major) bf16 copies of registered fused weights (the BERT layer

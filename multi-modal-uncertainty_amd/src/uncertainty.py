@@ -1,7 +1,7 @@
 """K-member deep ensemble x T-pass MC-dropout evaluation of MMBT, NLL and ECE.
 
 North-star feature (absent from the reference code).
-The K members share the architecture but not the weights; their 12 encoder layers
+The K members share the architecture but not the weights; their encoder layers
 run as ONE batched launch per op: every GEMM is batched over members (weight
 stride = one member's matrix), attention is weight-free so all K*T*B sequences
 go in one launch, and LayerNorm uses member-strided affine params
@@ -21,7 +21,6 @@ from . import kernels as K
 from .mmbt import LN_EPS, _mix, _seed
 
 bf16 = torch.bfloat16
-HID, FFN = 768, 3072
 
 
 class EnsembleMMBT:
@@ -35,7 +34,11 @@ class EnsembleMMBT:
         for m in self.members:
             m.eval()
             m.enc._prepare()
-        n_layers = len(self.members[0].enc._lw)
+        lws = self.members[0].enc._lw
+        n_layers = len(lws)
+        self.hid, self.ffn, self.heads = lws[0].hid, lws[0].ffn, lws[0].heads  # (one architecture)
+        if any((lw.hid, lw.ffn, lw.heads) != (self.hid, self.ffn, self.heads) for m in self.members for lw in m.enc._lw):
+            raise ValueError("EnsembleMMBT: the members must share one BERT shape")
         self.layers = []
         for i in range(n_layers):
             self.layers.append({k: torch.stack([getattr(m.enc._lw[i], k) for m in self.members]).contiguous()
@@ -48,10 +51,11 @@ class EnsembleMMBT:
         self.hidden_dropout, self.attn_dropout = enc0.hidden_dropout, enc0.attn_dropout
 
     def _layer(self, lw, X, R, km, nb, L, p_attn, p_hid, seeds, res_ln=None, out32=False):
-        """X bf16 [K*M, 768] + its f32 residual -> (Y, S2, mean2, rstd2, Y32): src/encoder.py
+        """X bf16 [K*M, H] + its f32 residual -> (Y, S2, mean2, rstd2, Y32): src/encoder.py
         layer_forward batched over the members (the same f32 hidden stream: R is the embeddings'
         f32 rows, or the previous layer's S2 whose LayerNorm the epilogue recomputes from
-        res_ln = (mean, rstd, gamma [K, 768], beta [K, 768]))."""
+        res_ln = (mean, rstd, gamma [K, H], beta [K, H]))."""
+        HID, FFN, HEADS = self.hid, self.ffn, self.heads
         Km, M = self.K, nb * L
         dev = X.device
         f32 = torch.float32
@@ -59,8 +63,8 @@ class EnsembleMMBT:
         K.gemm(X, HID, True, lw["wqkv16"], HID, True, qkv, 3 * HID, M, 3 * HID, HID, batch=Km, sA=M * HID,
                sB=3 * HID * HID, sC=M * 3 * HID, epi=K.epilogue(K.EPI_STORE, bias=lw["bqkv"], bias_bstride=3 * HID))
         O = torch.empty(Km * M, HID, dtype=bf16, device=dev)
-        lse = torch.empty(Km * nb * 12, L, dtype=torch.float32, device=dev)
-        K.attention_fwd(qkv, km, O, lse, Km * nb, L, 12, p_attn, seeds[0])
+        lse = torch.empty(Km * nb * HEADS, L, dtype=torch.float32, device=dev)
+        K.attention_fwd(qkv, km, O, lse, Km * nb, L, HEADS, p_attn, seeds[0])
         S1 = torch.empty(Km * M, HID, dtype=f32, device=dev)
         K.gemm(O, HID, True, lw["wo16"], HID, True, S1, HID, M, HID, HID, batch=Km, sA=M * HID, sB=HID * HID,
                sC=M * HID, epi=K.epilogue(K.EPI_BIAS_DROP_RES, bias=lw["bo"], bias_bstride=HID, residual=R,
@@ -101,6 +105,7 @@ class EnsembleMMBT:
         nb = T_mc * B
         M = nb * S
         dev = img.device
+        HID = self.hid
         X = torch.empty(self.K * M, HID, dtype=bf16, device=dev)
         X32 = torch.empty(self.K * M, HID, dtype=torch.float32, device=dev)
         km = torch.empty(self.K * nb, S, dtype=torch.float32, device=dev)
@@ -124,7 +129,7 @@ class EnsembleMMBT:
                                             (_mix(base, 3 * i), _mix(base, 3 * i + 1), _mix(base, 3 * i + 2)),
                                             rln, out32=i == n - 1)
             rln = (mu, rs, lw["ln2w"], lw["ln2b"])
-        h0 = Y32.view(self.K, nb, S, HID)[:, :, 0]                             # [K, nb, 768] f32
+        h0 = Y32.view(self.K, nb, S, HID)[:, :, 0]                             # [K, nb, H] f32
         pooled = torch.tanh(torch.baddbmm(self.pool_b.unsqueeze(1), h0, self.pool_w.transpose(1, 2)))
         out = torch.baddbmm(self.clf_b.unsqueeze(1), pooled, self.clf_w.transpose(1, 2))
         return out.view(self.K, T_mc, B, -1)

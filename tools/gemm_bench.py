@@ -2,7 +2,7 @@
 (M = 256 x 513 token rows), with hipBLASLt (torch.matmul) on the same shapes as a
 yardstick.  Random operands (zero-filled data inflates MFMA clocks).
 
-  python tools/gemm_bench.py [--rows 131328] [--iters 10]
+  python tools/gemm_bench.py [--rows 131328] [--iters 10] [--hidden 1024]
 """
 import argparse
 import os
@@ -12,8 +12,6 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "multi-modal-uncertainty_amd"))
 from src import kernels as K  # noqa: E402
-
-HID, FFN = 768, 3072
 
 
 def timed(fn, iters):
@@ -36,7 +34,9 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--cases", default="", help="comma-separated substrings: run only the matching cases")
     ap.add_argument("--no-ref", action="store_true", help="skip the hipBLASLt yardstick")
+    ap.add_argument("--hidden", type=int, default=768, help="768 (bert-base) or 1024 (bert-large); FFN = 4 x this")
     a = ap.parse_args()
+    HID, FFN = a.hidden, 4 * a.hidden
     M, dev, bf = a.rows, "cuda", torch.bfloat16
     g = torch.Generator(device=dev).manual_seed(0)
 
@@ -49,78 +49,78 @@ def main():
     Wqkv, Wo, W1, W2 = rnd(3 * HID, HID), rnd(HID, HID), rnd(FFN, HID), rnd(HID, FFN)
     Wqkvt, Wot, W1t, W2t = (w.t().contiguous() for w in (Wqkv, Wo, W1, W2))
     bqkv, bo, b1 = (torch.randn(n, device=dev) for n in (3 * HID, HID, FFN))
-    out768, out2304, out3072 = (torch.empty(M, n, dtype=bf, device=dev) for n in (HID, 3 * HID, FFN))
+    outH, out3H, outF = (torch.empty(M, n, dtype=bf, device=dev) for n in (HID, 3 * HID, FFN))
     Zs = rnd(M, FFN)
     gW = torch.zeros(FFN, HID, device=dev)
     gW2, gWq, gWo = torch.zeros(HID, FFN, device=dev), torch.zeros(3 * HID, HID, device=dev), torch.zeros(HID, HID, device=dev)
     cs = torch.zeros(FFN, device=dev)
     cases = [
         ("fwd qkv  X.Wqkv^T+b", M, 3 * HID, HID,
-         lambda: K.gemm(X, HID, True, Wqkv, HID, True, out2304, 3 * HID, M, 3 * HID, HID,
+         lambda: K.gemm(X, HID, True, Wqkv, HID, True, out3H, 3 * HID, M, 3 * HID, HID,
                         epi=K.epilogue(K.EPI_STORE, bias=bqkv)),
          lambda: torch.matmul(X, Wqkv.t())),
         ("fwd o    drop_res", M, HID, HID,
-         lambda: K.gemm(O, HID, True, Wo, HID, True, out768, HID, M, HID, HID,
+         lambda: K.gemm(O, HID, True, Wo, HID, True, outH, HID, M, HID, HID,
                         epi=K.epilogue(K.EPI_BIAS_DROP_RES, bias=bo, residual=X, drop_p=0.1, seed=1)),
          lambda: torch.matmul(O, Wo.t())),
         ("fwd ffn1 gelu", M, FFN, HID,
-         lambda: K.gemm(A, HID, True, W1, HID, True, out3072, FFN, M, FFN, HID,
+         lambda: K.gemm(A, HID, True, W1, HID, True, outF, FFN, M, FFN, HID,
                         epi=K.epilogue(K.EPI_BIAS_GELU, bias=b1, aux=Zs)),
          lambda: torch.matmul(A, W1.t())),
         ("fwd ffn1 gelu, no aux", M, FFN, HID,
-         lambda: K.gemm(A, HID, True, W1, HID, True, out3072, FFN, M, FFN, HID,
+         lambda: K.gemm(A, HID, True, W1, HID, True, outF, FFN, M, FFN, HID,
                         epi=K.epilogue(K.EPI_BIAS_GELU, bias=b1)),
          lambda: torch.matmul(A, W1.t())),
         ("fwd ffn1 bias only", M, FFN, HID,
-         lambda: K.gemm(A, HID, True, W1, HID, True, out3072, FFN, M, FFN, HID,
+         lambda: K.gemm(A, HID, True, W1, HID, True, outF, FFN, M, FFN, HID,
                         epi=K.epilogue(K.EPI_STORE, bias=b1)),
          lambda: torch.matmul(A, W1.t())),
         ("fwd o    bias only", M, HID, HID,
-         lambda: K.gemm(O, HID, True, Wo, HID, True, out768, HID, M, HID, HID,
+         lambda: K.gemm(O, HID, True, Wo, HID, True, outH, HID, M, HID, HID,
                         epi=K.epilogue(K.EPI_STORE, bias=bo)),
          lambda: torch.matmul(O, Wo.t())),
         ("fwd o    res, no dropout", M, HID, HID,
-         lambda: K.gemm(O, HID, True, Wo, HID, True, out768, HID, M, HID, HID,
+         lambda: K.gemm(O, HID, True, Wo, HID, True, outH, HID, M, HID, HID,
                         epi=K.epilogue(K.EPI_BIAS_DROP_RES, bias=bo, residual=X, drop_p=0.0, seed=1)),
          lambda: torch.matmul(O, Wo.t())),
         ("fwd ffn2 drop_res", M, HID, FFN,
-         lambda: K.gemm(Hh, FFN, True, W2, FFN, True, out768, HID, M, HID, FFN,
+         lambda: K.gemm(Hh, FFN, True, W2, FFN, True, outH, HID, M, HID, FFN,
                         epi=K.epilogue(K.EPI_BIAS_DROP_RES, bias=bo, residual=A, drop_p=0.1, seed=2)),
          lambda: torch.matmul(Hh, W2.t())),
         ("bwd dZ   dgelu+colsum", M, FFN, HID,
-         lambda: K.gemm(dY, HID, True, W2, FFN, False, out3072, FFN, M, FFN, HID,
+         lambda: K.gemm(dY, HID, True, W2, FFN, False, outF, FFN, M, FFN, HID,
                         epi=K.epilogue(K.EPI_DGELU, aux=Zs, colsum=cs)),
          lambda: torch.matmul(dY, W2)),
         ("bwd dA   add_res", M, HID, FFN,
-         lambda: K.gemm(dZ, FFN, True, W1, HID, False, out768, HID, M, HID, FFN,
+         lambda: K.gemm(dZ, FFN, True, W1, HID, False, outH, HID, M, HID, FFN,
                         epi=K.epilogue(K.EPI_ADD_RES, residual=dY)),
          lambda: torch.matmul(dZ, W1)),
         ("bwd dX   qkv add_res", M, HID, 3 * HID,
-         lambda: K.gemm(dqkv, 3 * HID, True, Wqkv, HID, False, out768, HID, M, HID, 3 * HID,
+         lambda: K.gemm(dqkv, 3 * HID, True, Wqkv, HID, False, outH, HID, M, HID, 3 * HID,
                         epi=K.epilogue(K.EPI_ADD_RES, residual=dY)),
          lambda: torch.matmul(dqkv, Wqkv)),
         ("bwd dO   store", M, HID, HID,
-         lambda: K.gemm(dY, HID, True, Wo, HID, False, out768, HID, M, HID, HID),
+         lambda: K.gemm(dY, HID, True, Wo, HID, False, outH, HID, M, HID, HID),
          lambda: torch.matmul(dY, Wo)),
         # the same data-grad products with a K-major (transposed) copy of the weight as B
         ("bwd dZ   B=W2^T kmaj", M, FFN, HID,
-         lambda: K.gemm(dY, HID, True, W2t, HID, True, out3072, FFN, M, FFN, HID,
+         lambda: K.gemm(dY, HID, True, W2t, HID, True, outF, FFN, M, FFN, HID,
                         epi=K.epilogue(K.EPI_DGELU, aux=Zs, colsum=cs)),
          lambda: torch.matmul(dY, W2)),
         ("bwd dZ   B=W2^T kmaj, no colsum", M, FFN, HID,
-         lambda: K.gemm(dY, HID, True, W2t, HID, True, out3072, FFN, M, FFN, HID,
+         lambda: K.gemm(dY, HID, True, W2t, HID, True, outF, FFN, M, FFN, HID,
                         epi=K.epilogue(K.EPI_DGELU, aux=Zs)),
          lambda: torch.matmul(dY, W2)),
         ("bwd dA   B=W1^T kmaj", M, HID, FFN,
-         lambda: K.gemm(dZ, FFN, True, W1t, FFN, True, out768, HID, M, HID, FFN,
+         lambda: K.gemm(dZ, FFN, True, W1t, FFN, True, outH, HID, M, HID, FFN,
                         epi=K.epilogue(K.EPI_ADD_RES, residual=dY)),
          lambda: torch.matmul(dZ, W1)),
         ("bwd dX   B=Wqkv^T kmaj", M, HID, 3 * HID,
-         lambda: K.gemm(dqkv, 3 * HID, True, Wqkvt, 3 * HID, True, out768, HID, M, HID, 3 * HID,
+         lambda: K.gemm(dqkv, 3 * HID, True, Wqkvt, 3 * HID, True, outH, HID, M, HID, 3 * HID,
                         epi=K.epilogue(K.EPI_ADD_RES, residual=dY)),
          lambda: torch.matmul(dqkv, Wqkv)),
         ("bwd dO   B=Wo^T kmaj", M, HID, HID,
-         lambda: K.gemm(dY, HID, True, Wot, HID, True, out768, HID, M, HID, HID),
+         lambda: K.gemm(dY, HID, True, Wot, HID, True, outH, HID, M, HID, HID),
          lambda: torch.matmul(dY, Wo)),
         ("wgrad W1 dZ^T.A f32acc", FFN, HID, M,
          lambda: K.gemm(dZ, FFN, False, A, HID, False, gW, HID, FFN, HID, M,
