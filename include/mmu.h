@@ -61,7 +61,10 @@ int mmu_set_seed_offset(const uint64_t* dev_counter);
  *     path, whatever MMU_GEMM_CS_PART says; batch > 1 with a colsum is refused (mmu_last_error);
  *   mmu_colsum_bf16 over more than 1024 rows needs its scratch table;
  *   mmu_embed_bwd needs the larger workspace mmu_embed_bwd_ws_floats() reports while the mode is
- *     on (16-B aligned). */
+ *     on (16-B aligned);
+ *   mmu_uncertainty_decompose launches the same kernel in both modes: it has no atomics, its
+ *     sums fold in a fixed lane and wave order, so its result depends on the inputs and the
+ *     shape alone and is bitwise repeatable with the mode on or off. */
 int mmu_set_deterministic(int on); /* -> the previous value */
 int mmu_get_deterministic(void);
 
@@ -562,6 +565,33 @@ int mmu_uncertainty(const float* logits, const int64_t* y, int64_t S, int64_t R,
 /* 15-style equal-width bins: out f32 [3*n_bins] = (count, sum conf, sum correct). */
 int mmu_ece_bins(const float* conf, const float* correct, int64_t S, int64_t n_bins,
                  float* out, mmu_stream_t stream);
+
+/* Entropy / mutual-information split of the K-member x T-pass prediction, per sample.
+ * logits f32, element (s, k, t, c) at logits[s*ss + k*sk + t*st + c]: element strides, class axis
+ * contiguous, so the [K, T, S, C] tensor of one batched ensemble forward (ss = C, st = S*C,
+ * sk = T*S*C) is read in place, and [S, K, T, C] too.  1 <= C <= 1024.  y int64 [S].
+ * With p_kt = softmax(logits[s, k, t, :]), p_k = mean_t p_kt, p = mean_k p_k and
+ * H[q] = -sum_c q_c ln q_c (nats, 0 ln 0 = 0), stats f32 [S, MMU_UNC_NSTAT] holds the columns
+ * below; p_bar f32 [S, C] = p; member_nll f32 [S, K] = -ln max(p_k[y], 1e-12), or NULL.
+ * Mutual information = MI_MEMBERS + MI_PASSES.  Argmax ties go to the lowest class.
+ * A stride below the extent it steps over (st < C, or sk / ss overlapping another axis; axes of
+ * extent 1 never step and are not looked at) is refused.  y outside [0, C) is the caller's error.
+ * No reference counterpart (the reference stops at the softmax mean, notebooks/utils.py:22-23). */
+enum {
+  MMU_UNC_TOTAL = 0,       /* H[p]                                                         */
+  MMU_UNC_ALEATORIC = 1,   /* mean_{k,t} H[p_kt]                                           */
+  MMU_UNC_MI_MEMBERS = 2,  /* H[p] - mean_k H[p_k]: between-member disagreement            */
+  MMU_UNC_MI_PASSES = 3,   /* mean_k H[p_k] - aleatoric: within-member MC-dropout disagreement */
+  MMU_UNC_BRIER = 4,       /* sum_c (p_c - 1[c == y])^2                                    */
+  MMU_UNC_NLL = 5,         /* -ln max(p_y, 1e-12), the floor of mmu_uncertainty            */
+  MMU_UNC_CONF = 6,        /* max_c p_c                                                    */
+  MMU_UNC_CORRECT = 7,     /* 1[argmax_c p_c == y]                                         */
+  MMU_UNC_VOTE_DISAGREEMENT = 8, /* 1 - (largest count of argmax_c p_kt over the K*T rows) / (K*T) */
+  MMU_UNC_NSTAT = 9
+};
+int mmu_uncertainty_decompose(const float* logits, int64_t ss, int64_t sk, int64_t st, const int64_t* y,
+                              int64_t S, int64_t K, int64_t T, int64_t C, float* stats, float* p_bar,
+                              float* member_nll, mmu_stream_t stream);
 
 /* ------------------------------------------------------------------ timing
  * Device-time of every mmu_gemm launch while enabled, bracketed by HIP events on

@@ -245,5 +245,8 @@ int64_t batchnorm_ws_bytes(int64_t C);
 void uncertainty_launch(const float* logits, const int64_t* y, int64_t S, int64_t R, int64_t C, float* p_bar,
                         float* nll, float* conf, float* correct, hipStream_t s);
 void ece_bins_launch(const float* conf, const float* correct, int64_t S, int64_t n_bins, float* out, hipStream_t s);
+void uncertainty_decompose_launch(const float* logits, int64_t ss, int64_t sk, int64_t st, const int64_t* y, int64_t S,
+                                  int64_t K, int64_t T, int64_t C, float* stats, float* p_bar, float* member_nll,
+                                  hipStream_t s);
 
 }  // namespace mmu

@@ -120,4 +120,189 @@ void ece_bins_launch(const float* conf, const float* correct, int64_t S, int64_t
                      (int)n_bins, out);
 }
 
+// ------------------------------------------------------------------ entropy / mutual-information split
+// One 4-wave block per sample.  For member k the waves share its T rows (wave w takes t = w, w + 4,
+// ...).  A lane owns classes lane, lane + 64, ..., NJ per lane (NJ * 64 >= C, NJ <= 16) in registers:
+// a logit row is loaded once, and its max / argmax vote, exp-sum, entropy ln Z - sum e^(z-m) (z-m) / Z
+// and its share of the member's p_k all come from those registers.  The waves' partial p_k meet in
+// LDS and are folded in wave order by the thread that owns the class (tid, tid + 256, ...), which
+// also keeps that class of p = mean_k p_k.  No atomics: every sum has one fixed order, so the result
+// depends on the inputs and the shape alone (the same launch in both modes of deterministic()).
+// The per-row and per-member entropies are summed over rows / members in f64 (a handful of adds).
+constexpr int UD_WAVES = 4;
+constexpr int UD_THREADS = 64 * UD_WAVES;
+
+// argmax butterfly: ties go to the lowest class; every lane ends with the same pair
+static __device__ __forceinline__ void wave_argmax(float& best, int& arg) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ob = __shfl_xor(best, o, 64);
+    const int oa = __shfl_xor(arg, o, 64);
+    if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
+  }
+}
+
+template <int NJ>
+__global__ __launch_bounds__(UD_THREADS) void uncertainty_decompose_kernel(
+    const float* __restrict__ logits, int64_t ss, int64_t sk, int64_t st, const int64_t* __restrict__ y, int64_t K,
+    int64_t T, int64_t C, float* __restrict__ stats, float* __restrict__ p_bar, float* __restrict__ member_nll) {
+  constexpr int NI = NJ * 64 > UD_THREADS ? NJ * 64 / UD_THREADS : 1;  // classes per thread in the fold
+  __shared__ float part[UD_WAVES][NJ * 64];
+  __shared__ double red_d[UD_WAVES][4];
+  __shared__ float red_f[UD_WAVES][2];
+  __shared__ int red_i[UD_WAVES][2];
+  const int64_t s = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t yy = y[s];
+  const float invT = 1.0f / (float)T;
+  float pacc[NI];   // sum_k p_k of the classes this thread folds
+  int votes[NJ];    // this wave's row-argmax counts of the classes this lane owns
+#pragma unroll
+  for (int i = 0; i < NI; ++i) pacc[i] = 0.f;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) votes[j] = 0;
+  float hk = 0.f;     // this thread's share of sum_k H[p_k]
+  double hrow = 0.0;  // this wave's sum of row entropies (wave-uniform)
+
+  for (int64_t k = 0; k < K; ++k) {
+    float acc[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[j] = 0.f;
+    for (int64_t t = wave; t < T; t += UD_WAVES) {
+      const float* z = logits + s * ss + k * sk + t * st;
+      float v[NJ];
+      float best = -__builtin_huge_valf();
+      int arg = lane;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const int c = lane + 64 * j;
+        v[j] = c < C ? z[c] : -__builtin_huge_valf();
+        if (v[j] > best) { best = v[j]; arg = c; }
+      }
+      wave_argmax(best, arg);
+      float se = 0.f, sd = 0.f;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const float d = v[j] - best;
+        const float e = lane + 64 * j < C ? expf(d) : 0.f;
+        v[j] = e;
+        se += e;
+        sd += e > 0.f ? e * d : 0.f;
+        votes[j] += arg == lane + 64 * j ? 1 : 0;
+      }
+      se = wave_sum(se);
+      sd = wave_sum(sd);
+      hrow += (double)(logf(se) - sd / se);
+      const float inv = 1.0f / se;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) acc[j] += v[j] * inv;
+    }
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+      if (lane + 64 * j < C) part[wave][lane + 64 * j] = acc[j];
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+      const int c = tid + UD_THREADS * i;
+      if (c < C) {
+        float pk = part[0][c];
+#pragma unroll
+        for (int w = 1; w < UD_WAVES; ++w) pk += part[w][c];
+        pk *= invT;
+        pacc[i] += pk;
+        if (pk > 0.f) hk -= pk * logf(pk);
+        if (member_nll && c == yy) member_nll[s * K + k] = -logf(fmaxf(pk, 1e-12f));
+      }
+    }
+    __syncthreads();
+  }
+
+  // p, its entropy / Brier score / argmax, and the vote counts folded over the waves
+#pragma unroll
+  for (int j = 0; j < NJ; ++j)
+    if (lane + 64 * j < C) part[wave][lane + 64 * j] = __int_as_float(votes[j]);
+  __syncthreads();
+  const float invK = 1.0f / (float)K;
+  float ent = 0.f, brier = 0.f, py = 0.f, best = -1.f;
+  int arg = tid, vote = 0;
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    const int c = tid + UD_THREADS * i;
+    if (c < C) {
+      const float p = pacc[i] * invK;
+      p_bar[s * C + c] = p;
+      if (p > 0.f) ent -= p * logf(p);
+      const float d = p - (c == yy ? 1.f : 0.f);
+      brier += d * d;
+      if (c == yy) py = p;
+      if (p > best) { best = p; arg = c; }
+      int n = 0;
+#pragma unroll
+      for (int w = 0; w < UD_WAVES; ++w) n += __float_as_int(part[w][c]);
+      vote = n > vote ? n : vote;
+    }
+  }
+  ent = wave_sum(ent);
+  hk = wave_sum(hk);
+  brier = wave_sum(brier);
+  py = wave_sum(py);  // one owner, the others hold 0
+  wave_argmax(best, arg);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const int ov = __shfl_xor(vote, o, 64);
+    vote = ov > vote ? ov : vote;
+  }
+  if (lane == 0) {
+    red_d[wave][0] = (double)ent;
+    red_d[wave][1] = (double)hk;
+    red_d[wave][2] = hrow;
+    red_d[wave][3] = (double)brier;
+    red_f[wave][0] = py;
+    red_f[wave][1] = best;
+    red_i[wave][0] = arg;
+    red_i[wave][1] = vote;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double e = 0.0, h = 0.0, r = 0.0, b = 0.0;
+    float p_y = 0.f, b0 = red_f[0][1];
+    int a0 = red_i[0][0], v0 = 0;
+    for (int w = 0; w < UD_WAVES; ++w) {
+      e += red_d[w][0];
+      h += red_d[w][1];
+      r += red_d[w][2];
+      b += red_d[w][3];
+      p_y += red_f[w][0];
+      if (red_f[w][1] > b0 || (red_f[w][1] == b0 && red_i[w][0] < a0)) { b0 = red_f[w][1]; a0 = red_i[w][0]; }
+      v0 = red_i[w][1] > v0 ? red_i[w][1] : v0;
+    }
+    const double rows = (double)K * (double)T;
+    const double hmem = h / (double)K, alea = r / rows;
+    float* o = stats + s * MMU_UNC_NSTAT;
+    o[MMU_UNC_TOTAL] = (float)e;
+    o[MMU_UNC_ALEATORIC] = (float)alea;
+    o[MMU_UNC_MI_MEMBERS] = (float)(e - hmem);
+    o[MMU_UNC_MI_PASSES] = (float)(hmem - alea);
+    o[MMU_UNC_BRIER] = (float)b;
+    o[MMU_UNC_NLL] = -logf(fmaxf(p_y, 1e-12f));
+    o[MMU_UNC_CONF] = b0;
+    o[MMU_UNC_CORRECT] = a0 == yy ? 1.f : 0.f;
+    o[MMU_UNC_VOTE_DISAGREEMENT] = (float)(1.0 - (double)v0 / rows);
+  }
+}
+
+void uncertainty_decompose_launch(const float* logits, int64_t ss, int64_t sk, int64_t st, const int64_t* y, int64_t S,
+                                  int64_t K, int64_t T, int64_t C, float* stats, float* p_bar, float* member_nll,
+                                  hipStream_t s) {
+#define MMU_UD_LAUNCH(NJ)                                                                                          \
+  hipLaunchKernelGGL(uncertainty_decompose_kernel<NJ>, dim3((unsigned)S), dim3(UD_THREADS), 0, s, logits, ss, sk, \
+                     st, y, K, T, C, stats, p_bar, member_nll)
+  if (C <= 64) MMU_UD_LAUNCH(1);
+  else if (C <= 128) MMU_UD_LAUNCH(2);
+  else if (C <= 256) MMU_UD_LAUNCH(4);
+  else if (C <= 512) MMU_UD_LAUNCH(8);
+  else MMU_UD_LAUNCH(16);
+#undef MMU_UD_LAUNCH
+}
+
 }  // namespace mmu

@@ -8,6 +8,12 @@ per op (src/uncertainty.py) and writes
   <save_path>/uncertainty_<phase>_logits.npy   [S, K, T, n_classes]
   <save_path>/uncertainty_<phase>_labels.npy   [S]
   <save_path>/uncertainty_<phase>_metrics.json {nll, ece, acc, n, K, T}
+With --decompose and / or --variants full img_only txt_only control_image control_text (any
+subset) the metrics gain "decomposition" (the full forward's entropy / mutual-information split,
+Brier score, vote disagreement, per-member NLL, ensemble gain and error-detection AUROCs:
+src/uncertainty.py UncertaintyMeter(decompose=True)) and "variants" (the same, with nll / ece / acc,
+per requested variant; every variant but full is a logits call of its own on the same batch and
+also writes <save_path>/uncertainty_<phase>_<variant>_logits.npy).
 Without --mmbt: the reference's FashionMNIST MIMO robustness pass (eval_robustness.py:42-121,
 BASELINE config 1's model family): each of the 4 quarter-crop views zeroed in turn (the
 weight-sharing model sees the other 3), predictions [4, S, heads, 10] and labels written as
@@ -47,7 +53,15 @@ FLAGS = [
     ("--gin_file", dict(nargs="*", default=[])), ("--gin_param", dict(nargs="*", default=[])),
     ("--data_dir", dict(type=str, default=None)), ("--sample_size", dict(type=int, default=None)),
     ("--synthetic_images", dict(action="store_true")),
+    # MMBT uncertainty mode: the entropy / mutual-information split, per modality variant
+    ("--decompose", dict(action="store_true")),
+    ("--variants", dict(nargs="+", default=["full"],
+                        choices=["full", "img_only", "txt_only", "control_image", "control_text"])),
 ]
+
+# --variants name -> EnsembleMMBT.logits(variant=...)
+VARIANTS = {"img_only": "img_only", "txt_only": "txt_only", "control_image": ("control", "image"),
+            "control_text": ("control", "text")}
 
 
 def get_args(parser):
@@ -85,19 +99,38 @@ def run_mmbt(args):
             _load_pretrained_model(m, p)
         members.append(m.to(dev))
     ens = EnsembleMMBT(members)
-    meter = UncertaintyMeter(args.n_bins)
-    all_logits, labels = [], []
+    # --decompose / --variants: the full forward's meter takes the [K, T, B, C] logits in place, and
+    # every other variant is a logits call of its own on the same batch with a meter of its own
+    decompose = args.decompose or list(args.variants) != ["full"]
+    extra = [v for v in dict.fromkeys(args.variants) if v != "full"]
+    meter = UncertaintyMeter(args.n_bins, decompose=decompose)
+    vmeters = {v: UncertaintyMeter(args.n_bins, decompose=True) for v in extra}
+    all_logits, labels, vlogits = [], [], {v: [] for v in extra}
     with torch.no_grad():
         for x, y in data[args.phase]:
             txt, segment, mask, img = (t.to(dev) for t in x)
             lo = ens.logits(txt, segment, mask, img, mc_samples=args.mc_samples)   # [K, T, B, C]
-            flat = lo.permute(2, 0, 1, 3).reshape(lo.shape[2], -1, lo.shape[3])  # [B, K*T, C]
-            meter.update(flat, y.to(dev))
+            if decompose:
+                meter.update(lo, y.to(dev))
+            else:
+                flat = lo.permute(2, 0, 1, 3).reshape(lo.shape[2], -1, lo.shape[3])  # [B, K*T, C]
+                meter.update(flat, y.to(dev))
             all_logits.append(lo.permute(2, 0, 1, 3).cpu())
             labels.append(y)
-    res = dict(meter.result(), K=len(members), T=args.mc_samples)
+            for v in extra:
+                lv = ens.logits(txt, segment, mask, img, mc_samples=args.mc_samples, variant=VARIANTS[v])
+                vmeters[v].update(lv, y.to(dev))
+                vlogits[v].append(lv.permute(2, 0, 1, 3).cpu())
+    full = meter.result()
+    res = dict({k: full[k] for k in ("nll", "ece", "acc", "n")}, K=len(members), T=args.mc_samples)
+    if decompose:
+        res["decomposition"] = {k: v for k, v in full.items() if k not in ("nll", "ece", "acc", "n")}
+        res["variants"] = {v: full if v == "full" else vmeters[v].result() for v in dict.fromkeys(args.variants)}
     os.makedirs(args.save_path, exist_ok=True)
     np.save(os.path.join(args.save_path, f"uncertainty_{args.phase}_logits.npy"), torch.cat(all_logits).numpy())
+    for v in extra:   # (the full forward's logits are the file above)
+        np.save(os.path.join(args.save_path, f"uncertainty_{args.phase}_{v}_logits.npy"),
+                torch.cat(vlogits[v]).numpy())
     np.save(os.path.join(args.save_path, f"uncertainty_{args.phase}_labels.npy"), torch.cat(labels).numpy())
     with open(os.path.join(args.save_path, f"uncertainty_{args.phase}_metrics.json"), "w") as f:
         json.dump(res, f, indent=1)

@@ -1092,6 +1092,41 @@ def ece_bins(conf, correct, n_bins, out):
     N.call("mmu_ece_bins", _ptr(conf), _ptr(correct), conf.numel(), n_bins, _ptr(out), _stream(conf))
 
 
+# include/mmu.h MMU_UNC_*: the columns of uncertainty_decompose's stats
+UNC_COLUMNS = ("total", "aleatoric", "mi_members", "mi_passes", "brier", "nll", "conf", "correct",
+               "vote_disagreement")
+UNC_NSTAT = len(UNC_COLUMNS)
+
+
+def uncertainty_decompose(logits, y, stats, p_bar, member_nll=None):
+    """logits f32 [S, K, T, C], any strides with a contiguous class axis (``lo.permute(2, 0, 1, 3)`` of the
+    [K, T, B, C] ensemble logits is read in place), y int64 [S] -> stats f32 [S, UNC_NSTAT] (columns
+    UNC_COLUMNS), p_bar f32 [S, C], member_nll f32 [S, K] or None (mmu_uncertainty_decompose)."""
+    who = "uncertainty_decompose"
+    _want(logits, torch.float32, "logits")
+    if logits.dim() != 4:
+        raise N.NativeError(f"{who}: logits must be 4-D [S, K, T, C], got {tuple(logits.shape)}")
+    S, Km, T, C = logits.shape
+    ss, sk, st, sc = logits.stride()
+    if sc != 1 and C > 1:
+        raise N.NativeError(f"{who}: the class axis of logits must be contiguous, got stride {sc}")
+    _want(y, torch.int64, "y")
+    if tuple(y.shape) != (S,) or not y.is_contiguous():
+        raise N.NativeError(f"{who}: y must be contiguous int64 [S] = [{S}], got {tuple(y.shape)}")
+    for name, t, shape in (("stats", stats, (S, UNC_NSTAT)), ("p_bar", p_bar, (S, C)),
+                           ("member_nll", member_nll, (S, Km))):
+        if t is None:
+            if name == "member_nll":
+                continue
+            raise N.NativeError(f"{who}: {name} is required")
+        _want(t, torch.float32, name)
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise N.NativeError(f"{who}: {name} must be contiguous f32 {list(shape)}, got {tuple(t.shape)}")
+    _dev_check(logits, y, stats, p_bar, member_nll)
+    N.call("mmu_uncertainty_decompose", _ptr(logits), ss, sk, st, _ptr(y), S, Km, T, C, _ptr(stats), _ptr(p_bar),
+           _ptr(member_nll), _stream(logits))
+
+
 _alg = {"on": False, "bytes": 0.0, "n": 0}
 
 

@@ -13,12 +13,17 @@ Metrics (mmu_uncertainty / mmu_ece_bins):
   p_bar = mean over the K*T rows of softmax(logits)    (notebooks/food101_robustness.py:25-36)
   NLL   = -mean log p_bar[y]      (== reference CrossEntropyLoss at K = T = 1, src/mmbt.py:243)
   ECE   = sum_b (n_b/N) |acc_b - conf_b| over 15 equal-width bins of max p_bar (build-defined)
+UncertaintyMeter(decompose=True) (mmu_uncertainty_decompose, the [K, T, B, C] logits read in place):
+  total = H[p_bar], aleatoric = mean_kt H[p_kt], mi_members = H[p_bar] - mean_k H[p_k],
+  mi_passes = mean_k H[p_k] - aleatoric, Brier, vote disagreement, per-member NLL, and the AUROC of
+  the uncertainty scores as detectors of the misclassified samples
+EnsembleMMBT.logits(variant=...) runs the same pass on the img-only / txt-only / control gathers.
 """
 import numpy as np
 import torch
 
 from . import kernels as K
-from .mmbt import LN_EPS, _mix, _seed
+from .mmbt import LN_EPS, _mix, _seed, control_indices
 
 bf16 = torch.bfloat16
 
@@ -94,14 +99,36 @@ class EnsembleMMBT:
                             param_stride=HID)
         return Y, S2, mean2, rstd2, Y32
 
+    VARIANTS = ("img_only", "txt_only", ("control", "image"), ("control", "text"))
+
+    def variant_indices(self, variant, Tt):
+        """the gather of MultimodalBertEncoder.forward_img_only / forward_txt_only / forward_control
+        over the n_img + 2 + Tt embedding rows; a control draw comes from the global torch RNG"""
+        n_img = self.members[0].enc.n_img
+        if variant == "img_only":
+            return torch.arange(n_img + 2)
+        if variant == "txt_only":
+            return torch.cat([torch.zeros(1, dtype=torch.long), torch.arange(Tt) + n_img + 2])
+        if variant == ("control", "image"):
+            return control_indices(n_img + 2 + Tt, n_img + 1)
+        if variant == ("control", "text"):
+            return control_indices(n_img + 2 + Tt, Tt)
+        raise ValueError(f"EnsembleMMBT.logits: variant must be None or one of {self.VARIANTS}, got {variant!r}")
+
     @torch.no_grad()
-    def logits(self, txt, mask, segment, img, mc_samples=1, mc_dropout=None):
-        """-> [K, T, B, n_classes] f32.  mc_dropout defaults to mc_samples > 1."""
+    def logits(self, txt, mask, segment, img, mc_samples=1, mc_dropout=None, variant=None):
+        """-> [K, T, B, n_classes] f32.  mc_dropout defaults to mc_samples > 1.
+        variant: None (the full forward), "img_only", "txt_only", ("control", "image") or
+        ("control", "text"): every member and pass runs on that gather of the embedding rows
+        (src/mmbt.py forward_img_only / forward_txt_only / forward_control).  A control draw is made
+        once per call, before anything else touches the torch RNG, and shared by all members and
+        passes: under one seed it is the draw of a member's own forward_control."""
+        vidx = None if variant is None else self.variant_indices(variant, txt.shape[1])
         mc = (mc_samples > 1) if mc_dropout is None else mc_dropout
         T_mc = int(mc_samples)
         B, Tt = txt.shape
         enc0 = self.members[0].enc
-        S = enc0.n_img + 2 + Tt
+        S = enc0.n_img + 2 + Tt if vidx is None else vidx.numel()
         nb = T_mc * B
         M = nb * S
         dev = img.device
@@ -110,7 +137,8 @@ class EnsembleMMBT:
         X32 = torch.empty(self.K * M, HID, dtype=torch.float32, device=dev)
         km = torch.empty(self.K * nb, S, dtype=torch.float32, device=dev)
         p_txt = self.hidden_dropout if mc else 0.0
-        idx = torch.arange(S, device=dev).repeat(T_mc, 1)  # T_mc copies of the identity gather
+        # T_mc copies of the identity gather, or of the variant's
+        idx = (torch.arange(S, device=dev) if vidx is None else vidx.to(dev)).repeat(T_mc, 1)
         txt, segment, mask = (t.contiguous().long() for t in (txt, segment, mask))
         for k, m in enumerate(self.members):
             e = m.enc
@@ -135,34 +163,108 @@ class EnsembleMMBT:
         return out.view(self.K, T_mc, B, -1)
 
 
-class UncertaintyMeter:
-    """Accumulates NLL / ECE bins / accuracy over batches with the HIP reduction kernels."""
+def auroc(score, positive):
+    """Area under the ROC curve of ``score`` detecting the ``positive`` samples: the rank statistic
+    (sum of the positives' ranks - n_pos (n_pos + 1) / 2) / (n_pos n_neg) with average ranks on ties,
+    in fp64.  None when the samples are all positive or all negative."""
+    score = np.asarray(score, dtype=np.float64).reshape(-1)
+    pos = np.asarray(positive).reshape(-1).astype(bool)
+    n_pos = int(pos.sum())
+    n_neg = pos.size - n_pos
+    if n_pos == 0 or n_neg == 0:
+        return None
+    _, inv, cnt = np.unique(score, return_inverse=True, return_counts=True)
+    last = np.cumsum(cnt).astype(np.float64)          # the highest 1-based rank of each tie group
+    ranks = (last - (cnt - 1) / 2.0)[inv]
+    return float((ranks[pos].sum() - n_pos * (n_pos + 1) / 2.0) / (n_pos * float(n_neg)))
 
-    def __init__(self, n_bins=15):
+
+class UncertaintyMeter:
+    """Accumulates NLL / ECE bins / accuracy over batches with the HIP reduction kernels.
+    decompose=True: the entropy / mutual-information split of mmu_uncertainty_decompose as well
+    (per-sample statistics kept on the host; see result())."""
+
+    def __init__(self, n_bins=15, decompose=False):
         self.n_bins = n_bins
+        self.decompose = decompose
         self.bins = None
         self.nll_sum = 0.0
         self.correct = 0.0
         self.count = 0
+        self.stats, self.member_nll = [], []   # decompose: per batch [S, UNC_NSTAT] / [S, K] fp64
 
-    def update(self, logits, y):
-        """logits [S, R, C] (R = members x passes), y [S]."""
+    def update(self, logits, y, layout="KTBC"):
+        """logits [S, R, C] (R = members x passes), y [S].
+        decompose=True: logits [K, T, B, C] as EnsembleMMBT.logits returns them (layout "KTBC", read in
+        place through their strides) or [S, K, T, C] (layout "SKTC")."""
+        if self.decompose:
+            return self._update_decompose(logits, y, layout)
         S, R, C = logits.shape
         dev = logits.device
         p_bar = torch.empty(S, C, dtype=torch.float32, device=dev)
         nll, conf, cor = (torch.empty(S, dtype=torch.float32, device=dev) for _ in range(3))
         K.uncertainty(logits.float().contiguous(), y.long().contiguous(), p_bar, nll, conf, cor)
-        bins = torch.empty(3 * self.n_bins, dtype=torch.float32, device=dev)
-        K.ece_bins(conf, cor, self.n_bins, bins)
-        b = bins.double().cpu().numpy()
-        self.bins = b if self.bins is None else self.bins + b
+        self._bin(conf, cor)
         self.nll_sum += float(nll.double().sum())
         self.correct += float(cor.double().sum())
         self.count += S
         return p_bar
 
+    def _bin(self, conf, cor):
+        bins = torch.empty(3 * self.n_bins, dtype=torch.float32, device=conf.device)
+        K.ece_bins(conf, cor, self.n_bins, bins)
+        b = bins.double().cpu().numpy()
+        self.bins = b if self.bins is None else self.bins + b
+
+    def _update_decompose(self, logits, y, layout):
+        if layout not in ("KTBC", "SKTC") or logits.dim() != 4:
+            raise ValueError("UncertaintyMeter(decompose=True).update: logits [K, T, B, C] (layout 'KTBC') or "
+                             f"[S, K, T, C] (layout 'SKTC'), got {tuple(logits.shape)} with layout {layout!r}")
+        lo = logits.float()                                  # (f32 already: no copy)
+        lo = lo.permute(2, 0, 1, 3) if layout == "KTBC" else lo   # a view: the kernel takes the strides
+        S, Km, _, C = lo.shape
+        dev = lo.device
+        stats = torch.empty(S, K.UNC_NSTAT, dtype=torch.float32, device=dev)
+        p_bar = torch.empty(S, C, dtype=torch.float32, device=dev)
+        mnll = torch.empty(S, Km, dtype=torch.float32, device=dev)
+        K.uncertainty_decompose(lo, y.long().contiguous(), stats, p_bar, mnll)
+        col = K.UNC_COLUMNS.index
+        nll, cor = stats[:, col("nll")], stats[:, col("correct")]
+        self._bin(stats[:, col("conf")].contiguous(), cor.contiguous())
+        self.nll_sum += float(nll.double().sum())
+        self.correct += float(cor.double().sum())
+        self.count += S
+        self.stats.append(stats.double().cpu().numpy())
+        self.member_nll.append(mnll.double().cpu().numpy())
+        return p_bar
+
+    def per_sample(self):
+        """decompose=True: the per-sample statistics seen so far, {column or "mi": fp64 [n]}"""
+        st = np.concatenate(self.stats)
+        out = {name: st[:, i] for i, name in enumerate(K.UNC_COLUMNS)}
+        out["mi"] = out["mi_members"] + out["mi_passes"]
+        return out
+
     def result(self):
+        """-> {nll, ece, acc, n}; decompose=True adds the mean of every statistic column ("nll" is that
+        mean already), "mi" = mi_members + mi_passes, "member_nll" (mean per member), "ensemble_gain" =
+        mean member NLL - ensemble NLL, and "auroc": how well total / mi / 1 - conf / vote_disagreement
+        rank the misclassified samples first (None when all samples are correct or all are wrong)."""
         bb = self.bins.reshape(self.n_bins, 3)
         ece = float(np.abs(bb[:, 2] - bb[:, 1]).sum() / max(self.count, 1))
-        return {"nll": self.nll_sum / max(self.count, 1), "ece": ece, "acc": self.correct / max(self.count, 1),
-                "n": self.count}
+        res = {"nll": self.nll_sum / max(self.count, 1), "ece": ece, "acc": self.correct / max(self.count, 1),
+               "n": self.count}
+        if not self.decompose:
+            return res
+        ps = self.per_sample()
+        for name in K.UNC_COLUMNS + ("mi",):
+            if name not in ("nll", "correct"):       # today's "nll" and "acc"
+                res[name] = float(ps[name].mean())
+        member = np.concatenate(self.member_nll).mean(axis=0)
+        res["member_nll"] = [float(v) for v in member]
+        res["ensemble_gain"] = float(member.mean()) - res["nll"]
+        wrong = ps["correct"] == 0
+        res["auroc"] = {name: auroc(score, wrong) for name, score in
+                        (("total", ps["total"]), ("mi", ps["mi"]), ("one_minus_conf", 1.0 - ps["conf"]),
+                         ("vote_disagreement", ps["vote_disagreement"]))}
+        return res
