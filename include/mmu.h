@@ -64,7 +64,7 @@ int mmu_set_seed_offset(const uint64_t* dev_counter);
  *     on (16-B aligned);
  *   mmu_uncertainty_decompose launches the same kernel in both modes: it has no atomics, its
  *     sums fold in a fixed lane and wave order, so its result depends on the inputs and the
- *     shape alone and is bitwise repeatable with the mode on or off. */
+ *     shape alone and is bitwise repeatable with the mode on or off; mmu_robustness_summary likewise. */
 int mmu_set_deterministic(int on); /* -> the previous value */
 int mmu_get_deterministic(void);
 
@@ -592,6 +592,47 @@ enum {
 int mmu_uncertainty_decompose(const float* logits, int64_t ss, int64_t sk, int64_t st, const int64_t* y,
                               int64_t S, int64_t K, int64_t T, int64_t C, float* stats, float* p_bar,
                               float* member_nll, mmu_stream_t stream);
+
+/* Modality-reliance summary of the robustness stack, per sample (the analysis the reference does in
+ * notebooks/food101_robustness.py + notebooks/utils.py on the saved [S, 3 + 2n, C] predictions:
+ * label probability per variant, experimental shift against the mean control shift, accuracy from
+ * the argmax of the head-mean logits; restated here, and the Jensen-Shannon columns added).
+ * logits f32, element (s, v, k, c) at logits[s*ss + v*sv + k*sk + c]: element strides, class axis
+ * contiguous, so the [V, B, C] tensor robustness_logits holds before its final transpose (ss = C,
+ * sv = B*C, K = 1) is read in place, and [S, V, K, C] too.  V = 3 + 2n variants, n >= 1, in the
+ * stack's order: 0 full, 1 image-only, 2 text-only, 3 .. 3+n-1 image controls, 3+n .. 3+2n-1 text
+ * controls.  K heads / members (1 for MMBT).  1 <= C <= 1024, 5 <= V <= 1023 odd.  y int64 [S].
+ * With p_v = mean_k softmax(logits[s, v, k, :]), H[q] = -sum_c q_c ln q_c (nats, 0 ln 0 = 0):
+ *   p_label[v] = p_v[y]
+ *   hit[v]     = 1[argmax_c mean_k logits[s, v, k, c] == y]   (the LOGITS' head mean; ties -> lowest class)
+ *   js[v]      = H[(p_v + p_0) / 2] - (H[p_v] + H[p_0]) / 2   (Jensen-Shannon divergence from the full
+ *                forward, in [0, ln 2]; the label-free companion of p_label[v] - p_label[0])
+ * A label outside [0, C) gives p_label = 0 and hit = 0 (class indices are compared with y, never
+ * indexed by it).  stats f32 [S, MMU_ROB_NSTAT] holds the columns below; per_variant f32 [S, 3, V]
+ * = (p_label, js, hit), or NULL.  Strides are checked as in mmu_uncertainty_decompose.  One launch,
+ * no atomics, every sum in one fixed order: bitwise repeatable in both determinism modes. */
+enum {
+  MMU_ROB_P_FULL = 0,            /* p_label[0]                                                  */
+  MMU_ROB_DP_IMAGE = 1,          /* p_label[1] - p_label[0]                                     */
+  MMU_ROB_DP_IMAGE_CONTROL = 2,  /* mean_i (p_label[3+i] - p_label[0]), i < n                   */
+  MMU_ROB_SD_IMAGE_CONTROL = 3,  /* population std (ddof 0) of those n differences              */
+  MMU_ROB_DP_TEXT = 4,           /* p_label[2] - p_label[0]                                     */
+  MMU_ROB_DP_TEXT_CONTROL = 5,   /* mean_i (p_label[3+n+i] - p_label[0])                        */
+  MMU_ROB_SD_TEXT_CONTROL = 6,   /* population std of those n differences                       */
+  MMU_ROB_JS_IMAGE = 7,          /* js[1]                                                       */
+  MMU_ROB_JS_IMAGE_CONTROL = 8,  /* mean_i js[3+i]                                              */
+  MMU_ROB_JS_TEXT = 9,           /* js[2]                                                       */
+  MMU_ROB_JS_TEXT_CONTROL = 10,  /* mean_i js[3+n+i]                                            */
+  MMU_ROB_HIT_FULL = 11,         /* hit[0]                                                      */
+  MMU_ROB_HIT_IMAGE = 12,        /* hit[1]                                                      */
+  MMU_ROB_HIT_TEXT = 13,         /* hit[2]                                                      */
+  MMU_ROB_ACC_IMAGE_CONTROL = 14,/* mean_i hit[3+i]                                             */
+  MMU_ROB_ACC_TEXT_CONTROL = 15, /* mean_i hit[3+n+i]                                           */
+  MMU_ROB_NSTAT = 16
+};
+int mmu_robustness_summary(const float* logits, int64_t ss, int64_t sv, int64_t sk, const int64_t* y,
+                           int64_t S, int64_t V, int64_t K, int64_t C, float* stats, float* per_variant,
+                           mmu_stream_t stream);
 
 /* ------------------------------------------------------------------ timing
  * Device-time of every mmu_gemm launch while enabled, bracketed by HIP events on

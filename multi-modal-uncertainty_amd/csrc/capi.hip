@@ -1162,4 +1162,37 @@ int mmu_uncertainty_decompose(const float* logits, int64_t ss, int64_t sk, int64
   return check_launch(who);
 }
 
+int mmu_robustness_summary(const float* logits, int64_t ss, int64_t sv, int64_t sk, const int64_t* y, int64_t S,
+                           int64_t V, int64_t K, int64_t C, float* stats, float* per_variant, mmu_stream_t stream) {
+  const char* who = "mmu_robustness_summary";
+  if (!logits) return fail("%s: logits is null", who);
+  if (!y) return fail("%s: y is null", who);
+  if (!stats) return fail("%s: stats is null", who);
+  if (S <= 0) return fail("%s: S = %lld must be positive", who, (long long)S);
+  if (K <= 0) return fail("%s: K = %lld must be positive", who, (long long)K);
+  if (C <= 0) return fail("%s: C = %lld must be positive", who, (long long)C);
+  if (V < 5) return fail("%s: V = %lld is fewer than the 5 variants of one control repeat (V = 3 + 2n)", who, (long long)V);
+  if (V % 2 == 0) return fail("%s: V = %lld must be odd (V = 3 + 2n)", who, (long long)V);
+  if (V > 1023) return fail("%s: V = %lld exceeds 1023 variants", who, (long long)V);
+  if (C > 1024) return fail("%s: C = %lld exceeds 1024 classes", who, (long long)C);
+  if (S > 0x7fffffffLL) return fail("%s: S = %lld exceeds the grid limit 2147483647", who, (long long)S);
+  // the axes that step (extent > 1), by ascending stride: each must clear the span of the one below it
+  struct Axis { const char* name; int64_t stride, extent; } ax[3] = {{"ss", ss, S}, {"sv", sv, V}, {"sk", sk, K}};
+  for (int i = 1; i < 3; ++i)
+    for (int j = i; j > 0 && ax[j].stride < ax[j - 1].stride; --j) std::swap(ax[j], ax[j - 1]);
+  int64_t span = C;
+  const char* below = "C";
+  for (const Axis& a : ax) {
+    if (a.extent == 1) continue;
+    if (a.stride < span)
+      return fail("%s: %s = %lld is smaller than the %lld elements the %s axis below it spans (overlapping layout)",
+                  who, a.name, (long long)a.stride, (long long)span, below);
+    if (a.stride > INT64_MAX / a.extent) return fail("%s: %s = %lld overflows", who, a.name, (long long)a.stride);
+    span = a.stride * a.extent;
+    below = a.name;
+  }
+  robustness_summary_launch(logits, ss, sv, sk, y, S, V, K, C, stats, per_variant, (hipStream_t)stream);
+  return check_launch(who);
+}
+
 }  // extern "C"

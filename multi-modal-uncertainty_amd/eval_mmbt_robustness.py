@@ -6,8 +6,13 @@ encoder passes grouped into 3 launches by sequence length).
 
 Writes robustness_<ckpt>_predictions_<phase>.npy  [S, 3 + 2*n_repeats, n_classes]
        robustness_<ckpt>_labels_<phase>.npy       [S]
+--summary additionally writes (and prints) the modality-reliance analysis of those predictions
+(src/robustness.py RelianceMeter on the kernels.robustness_summary rows):
+       robustness_<ckpt>_summary_<phase>.json     RelianceMeter.result() + n_repeats, seed, columns
+       robustness_<ckpt>_reliance_<phase>.npy     [S, len(columns)] fp64, the per-sample rows
 """
 import argparse
+import json
 import logging
 import os
 import sys
@@ -19,7 +24,7 @@ import torch  # noqa: E402
 
 from src import dataset  # noqa: E402
 from src.mmbt import MultimodalBertClf  # noqa: E402
-from src.robustness import robustness_logits  # noqa: E402
+from src.robustness import RelianceMeter, json_safe, robustness_logits  # noqa: E402
 from src.training_loop import _load_pretrained_model  # noqa: E402
 from src.utils import set_seed, torch_to  # noqa: E402
 
@@ -41,6 +46,8 @@ FLAGS = [
     ("--img_embed_pool_type", dict(type=str, default="avg", choices=["max", "avg"])),
     ("--img_hidden_sz", dict(type=int, default=2048)), ("--include_bn", dict(type=int, default=True)),
     ("--synthetic", dict(type=int, default=0, help="N synthetic samples instead of the dataset")),
+    ("--summary", dict(action="store_true", help="also write the modality-reliance summary (JSON) and its "
+                                                 "per-sample rows")),
 ]
 
 
@@ -80,11 +87,15 @@ def main(argv=None):
     model.to(dev)
     model.eval()
     preds, labels = [], []
+    meter = RelianceMeter(args.n_repeats) if args.summary else None
     with torch.no_grad():
         for x, y in data[args.phase]:
             x, y = torch_to(x, dev), torch_to(y, dev)
             txt, segment, mask, img = x  # collate order; model(*x) binds mask<-segment, segment<-mask
-            preds.append(robustness_logits(model, txt, segment, mask, img, args.n_repeats).float().cpu())
+            lo = robustness_logits(model, txt, segment, mask, img, args.n_repeats).float()
+            if meter is not None:
+                meter.update(lo, y)
+            preds.append(lo.cpu())
             labels.append(y.cpu())
     preds = torch.cat(preds).numpy()
     labels = torch.cat(labels).numpy()
@@ -95,6 +106,17 @@ def main(argv=None):
     S, M, C = preds.shape
     print("Gathered predictions of {} samples, {} variants, {} classes".format(S, M, C))
     print("Gathered labels of {} samples".format(len(labels)))
+    if meter is not None:
+        # strict JSON: an undefined figure (a correlation of a constant column, a mean over no samples) is null
+        summary = json_safe(dict(meter.result(), n_repeats=args.n_repeats, seed=args.seed,
+                                 columns=list(meter.columns)))
+        with open(os.path.join(args.save_path, f"robustness_{name}_summary_{args.phase}.json"), "w") as f:
+            json.dump(summary, f, indent=1, allow_nan=False)
+        rows = meter.per_sample()
+        np.save(os.path.join(args.save_path, f"robustness_{name}_reliance_{args.phase}.npy"),
+                np.stack([rows[c] for c in meter.columns], axis=1))
+        print(json.dumps(summary, allow_nan=False))
+        return summary
 
 
 if __name__ == "__main__":

@@ -1127,6 +1127,44 @@ def uncertainty_decompose(logits, y, stats, p_bar, member_nll=None):
            _ptr(member_nll), _stream(logits))
 
 
+# include/mmu.h MMU_ROB_*: the columns of robustness_summary's stats
+ROB_COLUMNS = ("p_full", "dp_image", "dp_image_control", "sd_image_control", "dp_text", "dp_text_control",
+               "sd_text_control", "js_image", "js_image_control", "js_text", "js_text_control", "hit_full",
+               "hit_image", "hit_text", "acc_image_control", "acc_text_control")
+ROB_NSTAT = len(ROB_COLUMNS)
+
+
+def robustness_summary(logits, y, stats, per_variant=None):
+    """logits f32 [S, V, K, C] (or [S, V, C]: K = 1), any strides with a contiguous class axis
+    (``lo.transpose(0, 1)`` of the [V, B, C] robustness tensor is read in place), V = 3 + 2n, y int64 [S]
+    -> stats f32 [S, ROB_NSTAT] (columns ROB_COLUMNS), per_variant f32 [S, 3, V] = (p_label, js, hit) or
+    None (mmu_robustness_summary)."""
+    who = "robustness_summary"
+    _want(logits, torch.float32, "logits")
+    if logits.dim() == 3:
+        logits = logits.unsqueeze(2)
+    if logits.dim() != 4:
+        raise N.NativeError(f"{who}: logits must be 4-D [S, V, K, C] or 3-D [S, V, C], got {tuple(logits.shape)}")
+    S, V, Km, C = logits.shape
+    ss, sv, sk, sc = logits.stride()
+    if sc != 1 and C > 1:
+        raise N.NativeError(f"{who}: the class axis of logits must be contiguous, got stride {sc}")
+    _want(y, torch.int64, "y")
+    if tuple(y.shape) != (S,) or not y.is_contiguous():
+        raise N.NativeError(f"{who}: y must be contiguous int64 [S] = [{S}], got {tuple(y.shape)}")
+    for name, t, shape in (("stats", stats, (S, ROB_NSTAT)), ("per_variant", per_variant, (S, 3, V))):
+        if t is None:
+            if name == "per_variant":
+                continue
+            raise N.NativeError(f"{who}: {name} is required")
+        _want(t, torch.float32, name)
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise N.NativeError(f"{who}: {name} must be contiguous f32 {list(shape)}, got {tuple(t.shape)}")
+    _dev_check(logits, y, stats, per_variant)
+    N.call("mmu_robustness_summary", _ptr(logits), ss, sv, sk, _ptr(y), S, V, Km, C, _ptr(stats), _ptr(per_variant),
+           _stream(logits))
+
+
 _alg = {"on": False, "bytes": 0.0, "n": 0}
 
 

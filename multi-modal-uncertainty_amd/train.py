@@ -13,6 +13,10 @@ Additions (all optional):
   --synthetic with --framework flava: seeded FLAVA embeddings (197 image + <= 77 text tokens)
   --deterministic    bitwise-repeatable steps (kernels.set_deterministic + MIOpen's deterministic
                      algorithms); recorded in <save_path>/run_meta.json; gin: train.deterministic=1
+  --reliance_every N   (MMBT) every N-th epoch, the modality-reliance summary of the robustness pass over
+                     the dev split as val_rel_* history columns (src/robustness.py RelianceCallback;
+                     --reliance_repeats control draws per modality, --reliance_steps batches at most);
+                     0 = off: the callback list and history.csv are those of a run without the flag
 --framework vilt is refused: the reference's setup_vilt needs the remote dandelin/vilt-b32-mlm
 weights and ViltProcessor; the ViLT training step itself is src.vilt.ViltTrainHIP.
 """
@@ -73,6 +77,10 @@ FLAGS = [
     ("--deterministic", dict(action="store_true", help="bitwise-repeatable training steps: the HIP kernels sum in "
                                                        "a fixed order (no float atomics) and MIOpen picks "
                                                        "deterministic conv algorithms (DESIGN.md, Determinism)")),
+    ("--reliance_every", dict(type=int, default=0, help="MMBT: log the modality-reliance summary of the dev split "
+                                                        "every N-th epoch (0 = off)")),
+    ("--reliance_repeats", dict(type=int, default=20, help="control draws per modality of that pass")),
+    ("--reliance_steps", dict(type=int, default=None, help="at most this many dev batches per pass (default all)")),
 ]
 
 
@@ -91,9 +99,42 @@ def apply_deterministic(args):
 
 def run_meta(args):
     """what <save_path>/run_meta.json records of a run"""
-    return {"framework": args.framework, "dataset": args.dataset, "model_type": args.model_type, "seed": args.seed,
+    meta = {"framework": args.framework, "dataset": args.dataset, "model_type": args.model_type, "seed": args.seed,
             "batch_size": args.batch_size, "synthetic": int(args.synthetic),
             "deterministic": bool(args.deterministic)}
+    if getattr(args, "reliance_every", 0) > 0:
+        meta.update(reliance_every=args.reliance_every, reliance_repeats=args.reliance_repeats,
+                    reliance_steps=args.reliance_steps)
+    return meta
+
+
+def check_reliance_args(args):
+    """--reliance_every is the MMBT robustness pass: there is none for FLAVA"""
+    if getattr(args, "reliance_every", 0) > 0 and args.framework != "mmbt":
+        raise SystemExit("--reliance_every: the modality-reliance pass is implemented for --framework mmbt only "
+                         f"(got --framework {args.framework})")
+    if getattr(args, "reliance_every", 0) < 0 or getattr(args, "reliance_repeats", 20) < 1:
+        raise SystemExit("--reliance_every must be >= 0 and --reliance_repeats >= 1")
+
+
+def reliance_callback(args, model, loader, device):
+    """the RelianceCallback of --reliance_every over the (per-rank) dev loader, or None when the flag is off"""
+    if getattr(args, "reliance_every", 0) <= 0:
+        return None
+    from src.robustness import RelianceCallback
+    return RelianceCallback(model, loader, device, n_repeats=args.reliance_repeats, every=args.reliance_every,
+                            steps=args.reliance_steps, seed=args.seed, prefix="val")
+
+
+def with_reliance(args, model, loader, device, callbacks):
+    """`callbacks` with the RelianceCallback of --reliance_every in front, so that the history callbacks
+    record its columns; the list itself when the flag is off.  device: where Model_.to put the model
+    (None: it was never moved to a GPU, which the pass needs)"""
+    if getattr(args, "reliance_every", 0) <= 0:
+        return callbacks
+    if device is None or torch.device(device).type != "cuda":
+        raise SystemExit("--reliance_every: the robustness pass runs on the GPU the model is on; pass --use_gpu")
+    return [reliance_callback(args, model, loader, device)] + list(callbacks)
 
 
 def add_conditional_args(args):
@@ -252,6 +293,7 @@ def main(argv=None):
     unused = gin.load(args, args.gin_file, args.gin_param)
     if unused:
         logger.warning("gin bindings not mapped to train.py flags: %s", sorted(unused))
+    check_reliance_args(args)
     args = add_conditional_args(args)
     set_seed(args.seed)
     apply_deterministic(args)
@@ -319,6 +361,8 @@ def main(argv=None):
         # evaluation sharded over the ranks, sample-weighted sums combined in eval_loop
         valid, test = (shard_eval_loader(dl, world, rank) for dl in (valid, test))
         m.shard_eval = True
+    # on every rank (the ranks exchange their shards' rows), ahead of the history callbacks that record it
+    callbacks = with_reliance(args, model, valid, m.device, callbacks)
     m.train_loop(train, valid_generator=valid, test_generator=test, steps_per_epoch=len(train),
                  validation_steps=len(valid), test_steps=len(test), epochs=args.n_epochs, callbacks=callbacks,
                  patience=args.patience, epoch_start=epoch_start, scheduler_step_on=args.scheduler_step_on,
