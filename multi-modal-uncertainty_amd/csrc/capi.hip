@@ -57,6 +57,10 @@ static int fail(const char* fmt, ...) {
   return 1;
 }
 
+// the conv / stem / pool kernels move 16 B per lane: every tensor they are given must start on a
+// 16-B boundary (a NULL optional pointer passes)
+static bool off16(const void* q) { return ((uintptr_t)q & 15) != 0; }
+
 static int check_launch(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail("%s: launch failed: %s", what, hipGetErrorString(e));
@@ -731,6 +735,7 @@ int mmu_maxpool_fwd(const void* x, int64_t B, int64_t H, int64_t W, int64_t C, v
                     mmu_stream_t stream) {
   if (!x || !y || !argmax || B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 || H > 65536 || W > 65536)
     return fail("mmu_maxpool_fwd: bad args");
+  if (off16(x) || off16(y) || off16(argmax)) return fail("mmu_maxpool_fwd: x, y and argmax must be 16-B aligned");
   maxpool3s2_fwd_launch((const bf16*)x, B, (int)H, (int)W, (int)C, (int)((H - 1) / 2 + 1), (int)((W - 1) / 2 + 1),
                         (bf16*)y, argmax, (hipStream_t)stream);
   return check_launch("mmu_maxpool_fwd");
@@ -740,6 +745,7 @@ int mmu_maxpool_bwd(const void* dy, const uint8_t* argmax, int64_t B, int64_t H,
                     mmu_stream_t stream) {
   if (!dy || !dx || !argmax || B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 || H > 65536 || W > 65536)
     return fail("mmu_maxpool_bwd: bad args");
+  if (off16(dy) || off16(dx) || off16(argmax)) return fail("mmu_maxpool_bwd: dy, dx and argmax must be 16-B aligned");
   maxpool3s2_bwd_launch((const bf16*)dy, argmax, B, (int)H, (int)W, (int)C, (int)((H - 1) / 2 + 1),
                         (int)((W - 1) / 2 + 1), (bf16*)dx, (hipStream_t)stream);
   return check_launch("mmu_maxpool_bwd");
@@ -748,6 +754,7 @@ int mmu_maxpool_bwd(const void* dy, const uint8_t* argmax, int64_t B, int64_t H,
 int mmu_row_pool_fwd(const void* fmap, int64_t B, int64_t Hh, int64_t Ww, int64_t C, int64_t n, float* out,
                      mmu_stream_t stream) {
   if (!fmap || !out || C % 8 || n <= 0 || n > Hh) return fail("mmu_row_pool_fwd: bad args");
+  if (off16(fmap) || off16(out)) return fail("mmu_row_pool_fwd: fmap and out must be 16-B aligned");
   row_pool_fwd_launch((const bf16*)fmap, B, Hh, Ww, C, n, out, (hipStream_t)stream);
   return check_launch("mmu_row_pool_fwd");
 }
@@ -755,6 +762,7 @@ int mmu_row_pool_fwd(const void* fmap, int64_t B, int64_t Hh, int64_t Ww, int64_
 int mmu_row_pool_bwd(const float* dout, int64_t B, int64_t Hh, int64_t Ww, int64_t C, int64_t n, void* dfmap,
                      mmu_stream_t stream) {
   if (!dout || !dfmap || C % 8 || n <= 0 || n > Hh) return fail("mmu_row_pool_bwd: bad args");
+  if (off16(dout) || off16(dfmap)) return fail("mmu_row_pool_bwd: dout and dfmap must be 16-B aligned");
   row_pool_bwd_launch(dout, B, Hh, Ww, C, n, (bf16*)dfmap, (hipStream_t)stream);
   return check_launch("mmu_row_pool_bwd");
 }
@@ -778,6 +786,8 @@ int mmu_conv_wgrad(const void* dY, const void* X, float* dW, int64_t n_img, int6
                    int64_t Cout, int64_t ksize, int64_t stride, int accumulate, float* ws, int64_t ws_floats,
                    mmu_stream_t stream) {
   if (!dY || !X || !dW) return fail("mmu_conv_wgrad: null pointer");
+  if (off16(dY) || off16(X) || off16(dW) || off16(ws))
+    return fail("mmu_conv_wgrad: dY, X, dW and the workspace must be 16-B aligned");
   if (Cin % 256 || Cout % 128 || Cin <= 0 || Cout <= 0)
     return fail("mmu_conv_wgrad: needs Cin %% 256 == 0, Cout %% 128 == 0 (Cin=%ld Cout=%ld)", Cin, Cout);
   GemmParams p{};
@@ -832,6 +842,7 @@ static int stem_params(StemParams& p, int64_t n_img, int64_t H, int64_t W, const
 int mmu_stem_conv_fwd(const void* X, const void* Wk, void* Y, int64_t n_img, int64_t H, int64_t W,
                       mmu_stream_t stream) {
   if (!X || !Wk || !Y) return fail("mmu_stem_conv_fwd: null pointer");
+  if (off16(X) || off16(Wk) || off16(Y)) return fail("mmu_stem_conv_fwd: X, Wk and Y must be 16-B aligned");
   StemParams p{};
   if (stem_params(p, n_img, H, W, "mmu_stem_conv_fwd")) return 1;
   p.X = (const bf16*)X; p.Wt = (const bf16*)Wk; p.Y = (bf16*)Y;
@@ -848,6 +859,8 @@ int64_t mmu_stem_conv_wgrad_ws_floats(int64_t n_img, int64_t H, int64_t W) {
 int mmu_stem_conv_wgrad(const void* dY, const void* X, float* dW, int64_t n_img, int64_t H, int64_t W,
                         int accumulate, float* ws, int64_t ws_floats, mmu_stream_t stream) {
   if (!dY || !X || !dW || !ws) return fail("mmu_stem_conv_wgrad: null pointer");
+  if (off16(dY) || off16(X) || off16(dW) || off16(ws))
+    return fail("mmu_stem_conv_wgrad: dY, X, dW and the workspace must be 16-B aligned");
   StemParams p{};
   if (stem_params(p, n_img, H, W, "mmu_stem_conv_wgrad")) return 1;
   if (ws_floats < stem_wgrad_ws_floats(p.n_tiles))
@@ -862,6 +875,9 @@ static int conv_implicit(const void* X, const void* Wk, void* Y, int64_t n_img, 
                          mmu_stream_t stream, const void* bn_x = nullptr, const uint8_t* bn_mask = nullptr,
                          const float* bn_mean = nullptr) {
   if (!X || !Wk || !Y) return fail("mmu_conv_implicit: null pointer");
+  // (bn_mask is read by the byte)
+  if (off16(X) || off16(Wk) || off16(Y) || off16(stats) || off16(ws) || off16(bn_x) || off16(bn_mean))
+    return fail("mmu_conv_implicit: X, Wk, Y, the table, the workspace, bn_x and bn_mean must be 16-B aligned");
   if (C % 64 || N % 64 || N <= 0)
     return fail("mmu_conv_implicit: needs C %% 64 == 0, N %% 64 == 0 (C=%ld N=%ld)", C, N);
   GemmParams p{};

@@ -719,45 +719,73 @@ def image_normalize(img_u8, mean, std, out):
     return out
 
 
+def _aligned(who, *ts):
+    """the conv / stem / pool kernels move 16 B per lane: a tensor that does not start on a 16-B
+    boundary (a view into the middle of a row) is refused"""
+    for t in ts:
+        if t is not None and t.data_ptr() % 16:
+            raise N.NativeError(f"{who}: a tensor {tuple(t.shape)} {t.dtype} is not 16-B aligned")
+
+
 def maxpool_fwd(x, y, argmax):
     """MaxPool2d(3, 2, 1) of a channels-last bf16 [B, C, H, W] map -> y [B, C, OH, OW]
     (channels-last) and the uint8 argmax in y's NHWC layout; see mmu_maxpool_fwd."""
+    _maxpool_check(x, y, argmax, "x", "y")
     _dev_check(x, y, argmax)
     B, C, H, W = x.shape
-    _maxpool_check(x, y, argmax, B, C, H, W, "x", "y")
     N.call("mmu_maxpool_fwd", _ptr(x), B, H, W, C, _ptr(y), _ptr(argmax), _stream(x))
 
 
 def maxpool_bwd(dy, argmax, dx):
+    _maxpool_check(dx, dy, argmax, "dx", "dy")
     _dev_check(dy, argmax, dx)
     B, C, H, W = dx.shape
-    _maxpool_check(dx, dy, argmax, B, C, H, W, "dx", "dy")
     N.call("mmu_maxpool_bwd", _ptr(dy), _ptr(argmax), B, H, W, C, _ptr(dx), _stream(dx))
 
 
-def _maxpool_check(full, pooled, argmax, B, C, H, W, nf, np_):
+def _maxpool_check(full, pooled, argmax, nf, np_):
     """The kernels index raw NHWC pointers: refuse any layout / size they do not assume."""
-    oshape = (B, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1)
     for t, nm in ((full, nf), (pooled, np_)):
         _want(t, torch.bfloat16, f"maxpool {nm}")
         if t.dim() != 4 or not t.is_contiguous(memory_format=torch.channels_last):
             raise N.NativeError(f"maxpool: {nm} must be a channels-last [B, C, H, W] bf16 map")
+    B, C, H, W = full.shape
+    oshape = (B, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1)
     if tuple(pooled.shape) != oshape:
         raise N.NativeError(f"maxpool: {np_} is {tuple(pooled.shape)}, MaxPool2d(3, 2, 1) of "
                             f"{(B, C, H, W)} is {oshape}")
     if argmax.dtype != torch.uint8 or argmax.numel() != pooled.numel() or not argmax.is_contiguous():
         raise N.NativeError("maxpool: argmax must be a contiguous uint8 tensor with one entry per pooled element")
+    _aligned("maxpool", full, pooled, argmax)
+
+
+def _row_pool_check(who, fmap, n, vec, nv):
+    """The kernels read fmap as raw [B][Hh][Ww][C] bf16 and vec as raw [B][n][C] f32."""
+    _want(fmap, torch.bfloat16, f"{who} fmap")
+    if fmap.dim() != 4 or not fmap.is_contiguous() or fmap.shape[3] % 8:
+        raise N.NativeError(f"{who}: fmap must be a contiguous [B, Hh, Ww, C] bf16 map with C % 8 == 0 "
+                            f"(got {tuple(fmap.shape)}, strides {tuple(fmap.stride())})")
+    B, Hh, Ww, C = fmap.shape
+    if not 1 <= n <= Hh:
+        raise N.NativeError(f"{who}: n = {n} rows must be within 1 .. Hh = {Hh}")
+    _want(vec, torch.float32, f"{who} {nv}")
+    if not vec.is_contiguous() or vec.numel() != B * n * C:
+        raise N.NativeError(f"{who}: {nv} must be a contiguous f32 tensor of B * n * C = {B * n * C} elements "
+                            f"(got {tuple(vec.shape)})")
+    _aligned(who, fmap, vec)
+    return B, Hh, Ww, C
 
 
 def row_pool_fwd(fmap_nhwc, n, out):
+    """AdaptiveAvgPool2d((n, 1)) of a contiguous bf16 [B, Hh, Ww, C] map -> out f32 [B, n, C]"""
+    B, Hh, Ww, C = _row_pool_check("row_pool_fwd", fmap_nhwc, n, out, "out")
     _dev_check(fmap_nhwc, out)
-    B, Hh, Ww, C = fmap_nhwc.shape
     N.call("mmu_row_pool_fwd", _ptr(fmap_nhwc), B, Hh, Ww, C, n, _ptr(out), _stream(out))
 
 
 def row_pool_bwd(dout, n, dfmap_nhwc):
+    B, Hh, Ww, C = _row_pool_check("row_pool_bwd", dfmap_nhwc, n, dout, "dout")
     _dev_check(dout, dfmap_nhwc)
-    B, Hh, Ww, C = dfmap_nhwc.shape
     N.call("mmu_row_pool_bwd", _ptr(dout), B, Hh, Ww, C, n, _ptr(dfmap_nhwc), _stream(dout))
 
 
@@ -772,9 +800,10 @@ def conv_implicit(X, Wk, Y, ksize=3, stride=1, stats=None):
     [N, Nout, Ho, Wo] channels-last bf16, Wk bf16 with memory [Nout][ksize][ksize][C] (a
     channels-last [Nout, C, k, k] filter, or the flipped-transposed 3x3 one for dX).
     stats (optional, bn_stats_table of Y's rows): Y's BatchNorm statistics, written too."""
-    _dev_check(X, Wk, Y)
     _want(X, torch.bfloat16, "conv_implicit X")
     _want(Wk, torch.bfloat16, "conv_implicit Wk")
+    if X.dim() != 4 or Y.dim() != 4:
+        raise N.NativeError("conv_implicit: X and Y must be 4-D [N, C, H, W] maps")
     n, c, h, w = X.shape
     nout = Y.shape[1]
     ho, wo = _conv_out(h, w, ksize, stride)
@@ -789,10 +818,13 @@ def conv_implicit(X, Wk, Y, ksize=3, stride=1, stats=None):
             or not X.is_contiguous(memory_format=cl) or not Y.is_contiguous(memory_format=cl)):
         raise N.NativeError(f"conv_implicit: X channels-last bf16 [N, C, H, W], Y [N, Nout, {ho}, {wo}], "
                             f"Wk [Nout][{k}][{k}][C] bf16")
+    if stats is not None and (stats.dtype != torch.float32 or not stats.is_contiguous()
+                              or stats.numel() < ((n * ho * wo + 63) // 64) * nout * 2):
+        raise N.NativeError("conv_implicit: stats table too small (kernels.bn_stats_table)")
+    _aligned("conv_implicit", X, Wk, Y, stats)
+    _dev_check(X, Wk, Y, stats)
     ws = _splitk_workspace(Y.device)  # split-K slabs for small maps (few tiles)
     if stats is not None:
-        if stats.dtype != torch.float32 or stats.numel() < ((n * ho * wo + 63) // 64) * nout * 2:
-            raise N.NativeError("conv_implicit: stats table too small (kernels.bn_stats_table)")
         N.call("mmu_conv_implicit_stats", _ptr(X), _ptr(Wk), _ptr(Y), n, h, w, c, nout, ksize, stride, _ptr(stats),
                _ptr(ws), ws.numel(), _stream(X))
         return
@@ -807,9 +839,9 @@ def conv3x3_implicit(X, Wk, Y, bnb=None, table=None):
     if bnb is None:
         conv_implicit(X, Wk, Y, 3, 1)
         return
-    _dev_check(X, Wk, Y, table)
     x, mask, mean = bnb
-    _bnb_check(x, mask, mean, "conv3x3_implicit bnb")
+    if X.dim() != 4 or Y.dim() != 4 or x.dim() != 4 or table is None:
+        raise N.NativeError("conv3x3_implicit bnb: X, Y and x must be 4-D [N, C, H, W] maps, with a table")
     n, c, h, w = X.shape
     nout = Y.shape[1]
     cl = torch.channels_last
@@ -817,8 +849,11 @@ def conv3x3_implicit(X, Wk, Y, bnb=None, table=None):
             or Wk.dtype != torch.bfloat16 or tuple(Wk.shape) != (nout, 3, 3, c) or not Wk.is_contiguous()
             or not X.is_contiguous(memory_format=cl) or not Y.is_contiguous(memory_format=cl)):
         raise N.NativeError("conv3x3_implicit bnb: X / Y / x channels-last bf16, Wk [Nout][3][3][C] bf16")
-    if table.dtype != torch.float32 or table.numel() < ((n * h * w + 63) // 64) * nout * 2:
+    if table.dtype != torch.float32 or not table.is_contiguous() or table.numel() < ((n * h * w + 63) // 64) * nout * 2:
         raise N.NativeError("conv3x3_implicit bnb: table too small (kernels.bn_stats_table)")
+    _aligned("conv3x3_implicit bnb", X, Wk, Y, table, x, mean)
+    _bnb_check(x, mask, mean, "conv3x3_implicit bnb")
+    _dev_check(X, Wk, Y, table, x, mean)
     ws = _splitk_workspace(Y.device)
     N.call("mmu_conv3x3_implicit_bnb", _ptr(X), _ptr(Wk), _ptr(Y), n, h, w, c, nout, _ptr(x), _ptr(mask),
            _ptr(mean), _ptr(table), _ptr(ws), ws.numel(), _stream(X))
@@ -834,7 +869,6 @@ def stem_conv_fwd(X, Wk, Y):
     """Y = conv2d(X, Wk, stride 2, padding 3): the ResNet stem (7x7, 3 -> 64).  X [N, 3, H, W]
     and Y [N, 64, Ho, Wo] channels-last bf16; Wk bf16 [64, 3, 7, 7] channels-last (memory
     [64][7][7][3], the parameter store's filter copy)."""
-    _dev_check(X, Wk, Y)
     _stem_check(X, "stem_conv_fwd")
     n, _, h, w = X.shape
     ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
@@ -844,13 +878,14 @@ def stem_conv_fwd(X, Wk, Y):
     if (tuple(Y.shape) != (n, 64, ho, wo) or Y.dtype != torch.bfloat16
             or not Y.is_contiguous(memory_format=torch.channels_last)):
         raise N.NativeError(f"stem_conv_fwd: Y must be channels-last bf16 [{n}, 64, {ho}, {wo}]")
+    _aligned("stem_conv_fwd", X, Wk, Y)
+    _dev_check(X, Wk, Y)
     N.call("mmu_stem_conv_fwd", _ptr(X), _ptr(Wk), _ptr(Y), n, h, w, _stream(X))
 
 
 def stem_conv_wgrad(dY, X, dW, accumulate=False):
     """dW (+)= the stem conv's filter gradient: dY [N, 64, Ho, Wo] and X [N, 3, H, W]
     channels-last bf16, dW f32 [64, 3, 7, 7] channels-last."""
-    _dev_check(dY, X, dW)
     _stem_check(X, "stem_conv_wgrad")
     n, _, h, w = X.shape
     ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
@@ -860,6 +895,8 @@ def stem_conv_wgrad(dY, X, dW, accumulate=False):
     if (tuple(dW.shape) != (64, 3, 7, 7) or dW.dtype != torch.float32
             or not dW.is_contiguous(memory_format=torch.channels_last)):
         raise N.NativeError("stem_conv_wgrad: dW must be channels-last f32 [64, 3, 7, 7]")
+    _aligned("stem_conv_wgrad", dY, X, dW)
+    _dev_check(dY, X, dW)
     need = N.load().mmu_stem_conv_wgrad_ws_floats(n, h, w)
     ws = _splitk_workspace(X.device)
     if need < 0 or ws.numel() < need:
@@ -872,9 +909,10 @@ def conv_wgrad(dY, X, dW, ksize=3, stride=1, accumulate=False):
     """dW (+)= weight gradient of a ksize x ksize (3: pad 1, 1: pad 0) / stride conv: X [N, Cin,
     H, W] and dY [N, Cout, Ho, Wo] channels-last bf16, dW f32 [Cout, Cin, k, k] channels-last
     (memory [Cout][k][k][Cin]).  Cin % 256 == 0, Cout % 128 == 0."""
-    _dev_check(dY, X, dW)
     _want(X, torch.bfloat16, "conv_wgrad X")
     _want(dY, torch.bfloat16, "conv_wgrad dY")
+    if X.dim() != 4 or dY.dim() != 4:
+        raise N.NativeError("conv_wgrad: X and dY must be 4-D [N, C, H, W] maps")
     n, cin, h, w = X.shape
     cout = dY.shape[1]
     ho, wo = _conv_out(h, w, ksize, stride)
@@ -884,6 +922,8 @@ def conv_wgrad(dY, X, dW, ksize=3, stride=1, accumulate=False):
             or not dW.is_contiguous(memory_format=cl)):
         raise N.NativeError(f"conv_wgrad: X channels-last bf16 [N, C, H, W], dY [N, Cout, {ho}, {wo}], "
                             f"dW f32 channels-last [Cout, Cin, {ksize}, {ksize}]")
+    _aligned("conv_wgrad", dY, X, dW)
+    _dev_check(dY, X, dW)
     ws = _splitk_workspace(X.device)
     N.call("mmu_conv_wgrad", _ptr(dY), _ptr(X), _ptr(dW), n, h, w, cin, cout, ksize, stride, int(bool(accumulate)),
            _ptr(ws), ws.numel(), _stream(X))
