@@ -36,7 +36,7 @@ enum { MMU_BF16 = 0, MMU_F32 = 1 };
  * mmu_embed_bwd_ws_floats().  4 (round 6): mmu_epilogue grows bn_x / bn_mask / bn_mean (the
  * BatchNorm-backward epilogues STORE_BNB / ADD_RES_BNB).  Still 4 with mmu_embed_bwd_ws_floats_h
  * and H = 1024 in mmu_embed_fwd / _bwd (a new symbol and a newly accepted value; no argument list
- * changed).  Callers compare mmu_version() with the header they were built against. */
+ * changed), and with the mmu_*_plan queries (new symbols).  Callers compare mmu_version() with the header they were built against. */
 #define MMU_ABI_VERSION 4
 int mmu_version(void);
 const char* mmu_last_error(void);
@@ -633,6 +633,51 @@ enum {
 int mmu_robustness_summary(const float* logits, int64_t ss, int64_t sv, int64_t sk, const int64_t* y,
                            int64_t S, int64_t V, int64_t K, int64_t C, float* stats, float* per_variant,
                            mmu_stream_t stream);
+
+/* ------------------------------------------------------------------ launch plans
+ * What the host would decide for a product -- tiling, tile order, split-K, the split tail rows, the
+ * column-sum path, the BatchNorm row blocks -- without launching it.  Each query runs the very
+ * function the launch runs (csrc/plan.h; bn_grid of csrc/batchnorm.hip), makes no HIP call and
+ * works without a GPU; a shape the launch would refuse is refused here with the same message
+ * (mmu_last_error).  `plan` receives MMU_*_PLAN_FIELDS int64 values in the order listed.
+ *
+ * mmu_gemm_plan: the plan of mmu_gemm / mmu_gemm_rows for this shape, under the MMU_GEMM_*
+ * environment knobs and the deterministic switch as they stand at the call, with both per-stream
+ * scratch slots assumed available (a launch that cannot have one -- first use under stream capture,
+ * a failed allocation -- drops the tail split / falls back to atomics).  has_bias / has_colsum: the
+ * epilogue's bias / colsum pointers are given; workspace_floats: its split-K workspace (0: none).
+ *    0 tiling      0 = 128 x 128, 1 = 256 x 256, 2 = 256 x 384
+ *    1 tiles_m     2 tiles_n     tiles of the whole product in that tiling
+ *    3 group_m     tile-order group height
+ *    4 splitk      5 kchunk      K slices and their depth (1, K: unsplit)
+ *    6 m_main      7 tail_rows   rows [m_main, M) are the split tail rows (M, 0: none); the main
+ *                                tiling then runs m_main / 256 tile rows
+ *    8 tail_split  9 tail_chunk  their K slices and depth (1, K: none)
+ *   10 cs          column sums: 0 = none, 1 = float atomics, 2 = partial rows, 3 = the float2 table
+ *   11 cs_rows    12 cs_parts    partial rows: rows per part on the main tiling (64 on the tail
+ *                                rows), and the parts in all
+ * mmu_conv_implicit_plan (mmu_conv_implicit[_stats], mmu_conv3x3_implicit[_bnb]):
+ *    0 small (1 = the 128 x 128 kernel, 0 = 256 x 256)   1 M = n Ho Wo   2 K = ksize^2 C   3 Ho   4 Wo
+ *    5 tiles_m   6 tiles_n   7 splitk   8 kchunk
+ * mmu_conv_wgrad_plan (mmu_conv_wgrad, mmu_conv3x3_wgrad):
+ *    0 K = n Ho Wo   1 Ho   2 Wo   3 tiles_m   4 tiles_n   5 few (1: <= 4 output tiles)   6 splitk   7 kchunk
+ * mmu_batchnorm_plan (the row-block grid of every mmu_batchnorm_* reduction and apply pass):
+ *    0 CH (channels per block)   1 rpi (rows per block iteration)   2 rpb (rows per block)
+ *    3 blocks (grid.x = block partials per channel)   4 gy (grid.y = C / CH)
+ *    5 clamped (1: rpb was raised so that blocks x C partial pairs fit the scratch)
+ */
+#define MMU_GEMM_PLAN_FIELDS 13
+#define MMU_CONV_IMPLICIT_PLAN_FIELDS 9
+#define MMU_CONV_WGRAD_PLAN_FIELDS 8
+#define MMU_BATCHNORM_PLAN_FIELDS 6
+int mmu_gemm_plan(int64_t M, int64_t N, int64_t K, int64_t batch, int64_t lda, int64_t ldb, int a_kmajor,
+                  int b_kmajor, int c_dtype, int kind, int has_bias, int has_colsum, int64_t workspace_floats,
+                  int64_t* plan);
+int mmu_conv_implicit_plan(int64_t n_img, int64_t H, int64_t W, int64_t C, int64_t N, int64_t ksize,
+                           int64_t stride, int64_t ws_floats, int64_t* plan);
+int mmu_conv_wgrad_plan(int64_t n_img, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int64_t ksize,
+                        int64_t stride, int64_t ws_floats, int64_t* plan);
+int mmu_batchnorm_plan(int64_t rows, int64_t C, int64_t* plan);
 
 /* ------------------------------------------------------------------ timing
  * Device-time of every mmu_gemm launch while enabled, bracketed by HIP events on

@@ -380,9 +380,10 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_apply_kernel(const bf16* __
 
 // ------------------------------------------------------------------------------ launchers
 struct BnGrid {
-  int CH;
+  int CH, rpi;
   int64_t rpb;
   dim3 grid;
+  bool clamped;  // rpb raised past its target so that the block partials fit BN_MAX_PART_ELEMS
 };
 // channel chunk: the largest of 512, 256, ..., 8 dividing C.  Rows per block: the tensor
 // split into ~BN_TARGET_BLOCKS blocks, but each block between BN_MIN and 64 K elements (a
@@ -398,19 +399,25 @@ static BnGrid bn_grid(int64_t rows, int C) {
   BnGrid g;
   g.CH = 512;
   while (C % g.CH) g.CH >>= 1;
-  const int rpi = BN_THREADS / (g.CH / 8);
+  const int rpi = g.rpi = BN_THREADS / (g.CH / 8);
   int64_t per = rows * (int64_t)C / target;
   per = per < min_elems ? min_elems : per > BN_ELEMS_PER_BLOCK ? BN_ELEMS_PER_BLOCK : per;
   int64_t rpb = (per + g.CH - 1) / g.CH;
   rpb = (rpb + rpi - 1) / rpi * rpi;
   const int64_t max_parts = BN_MAX_PART_ELEMS / C;
-  if ((rows + rpb - 1) / rpb > max_parts) rpb = ((rows + max_parts - 1) / max_parts + rpi - 1) / rpi * rpi;
+  g.clamped = (rows + rpb - 1) / rpb > max_parts;
+  if (g.clamped) rpb = ((rows + max_parts - 1) / max_parts + rpi - 1) / rpi * rpi;
   g.rpb = rpb;
   g.grid = dim3((unsigned)((rows + rpb - 1) / rpb), (unsigned)(C / g.CH));
   return g;
 }
 
 int64_t batchnorm_ws_bytes(int64_t C) { return BN_MAX_PART_ELEMS * 8 + ((3 * C + 3) & ~3) * 4; }
+
+void batchnorm_plan(int64_t rows, int64_t C, int64_t plan[MMU_BATCHNORM_PLAN_FIELDS]) {
+  const BnGrid G = bn_grid(rows, (int)C);
+  plan[0] = G.CH; plan[1] = G.rpi; plan[2] = G.rpb; plan[3] = G.grid.x; plan[4] = G.grid.y; plan[5] = G.clamped;
+}
 
 void batchnorm_fwd_launch(const BnFwdParams& q, hipStream_t s) {
   const BnGrid G = bn_grid(q.rows, q.C);

@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 #include "mmu_internal.h"
+#include "plan.h"
 #include <cstdlib>
 #include <cmath>
 
@@ -57,6 +58,11 @@ static int fail(const char* fmt, ...) {
   return 1;
 }
 
+// a plan function's refusal (plan.h): its format over the plan's `why` values
+static int refused(const char* fmt, const int64_t (&why)[6]) {
+  return fail(fmt, why[0], why[1], why[2], why[3], why[4], why[5]);
+}
+
 // the conv / stem / pool kernels move 16 B per lane: every tensor they are given must start on a
 // 16-B boundary (a NULL optional pointer passes)
 static bool off16(const void* q) { return ((uintptr_t)q & 15) != 0; }
@@ -89,11 +95,10 @@ std::pair<hipEvent_t, hipEvent_t> take_events() {
   }
   return ev;
 }
-// per-(device, stream) f32 scratch for the split tail rows of mmu_gemm: 32 MiB, allocated on first
-// use outside stream capture (NULL: the product runs without the tail split)
-constexpr int64_t TAIL_WS_FLOATS = 8ll << 20;
+// per-(device, stream) f32 scratch of mmu_gemm, TAIL_WS_FLOATS (plan.h) per slot, allocated on first
+// use outside stream capture (NULL: the product is planned again without that slot)
 // (slot 0: the split tail's slabs, slot 1: the column-sum partial rows)
-float* tail_workspace(int64_t floats, hipStream_t s, int slot = 0) {
+float* tail_workspace(int64_t floats, hipStream_t s, int slot) {
   static std::mutex mu;
   static std::map<std::tuple<int, hipStream_t, int>, float*> bufs;
   if (floats > TAIL_WS_FLOATS) return nullptr;
@@ -150,16 +155,27 @@ int mmu_timing_read(double* total_ms, int64_t* launches, double* flops) {
   return 0;
 }
 
-// mmu_gemm / mmu_gemm_rows: the dropout counter of row m is that of row drop_row_off + m drop_row_step
+// the MMU_GEMM_* environment knobs and the deterministic switch of one mmu_gemm call (read per
+// call, ~1 us: tests switch them inside one process)
+static GemmKnobs gemm_knobs() {
+  GemmKnobs kn;
+  if (const char* e = getenv("MMU_GEMM_WIDE")) kn.wide_mode = atoi(e);
+  if (const char* e = getenv("MMU_GEMM_WIDE_MIN_TILES")) kn.wide_min_tiles = (int64_t)atoll(e);
+  if (const char* e = getenv("MMU_GEMM_TAIL")) kn.tail_mode = atoi(e);
+  if (const char* e = getenv("MMU_GEMM_CS_PART")) kn.cs_part = atoi(e);
+  kn.deterministic = deterministic();
+  return kn;
+}
+
+// mmu_gemm / mmu_gemm_rows: the dropout counter of row m is that of row drop_row_off + m drop_row_step.
+// Validate (pointers, alignment, epilogue combinations), plan (plan.h: the shape rules and every
+// choice), take the scratch the plan asks for, launch from the plan.  Nothing is enqueued before
+// the last refusal.
 static int gemm_impl(const void* A, int64_t lda, int a_kmajor, const void* B, int64_t ldb, int b_kmajor, void* C,
                      int64_t ldc, int c_dtype, int64_t M, int64_t N, int64_t K, int64_t batch, int64_t strideA,
                      int64_t strideB, int64_t strideC, const mmu_epilogue* epi, int64_t drop_row_step,
                      int64_t drop_row_off, mmu_stream_t stream) {
   if (!A || !B || !C) return fail("mmu_gemm: null operand");
-  if (M <= 0 || N <= 0 || K <= 0 || batch <= 0) return fail("mmu_gemm: bad shape M=%ld N=%ld K=%ld", M, N, K);
-  if (N % 128) return fail("mmu_gemm: N=%ld must be a multiple of 128", N);
-  if ((a_kmajor || b_kmajor) && K % 64) return fail("mmu_gemm: K=%ld must be a multiple of 64 for a K-major operand", K);
-  if (!a_kmajor && M % 128) return fail("mmu_gemm: M=%ld must be a multiple of 128 when A is M-major", M);
   if ((lda % 8) || (ldb % 8) || (ldc % 4)) return fail("mmu_gemm: leading dims must be 16-B aligned");
   if (c_dtype != MMU_BF16 && c_dtype != MMU_F32) return fail("mmu_gemm: bad c_dtype");
   GemmParams p{};
@@ -167,23 +183,7 @@ static int gemm_impl(const void* A, int64_t lda, int a_kmajor, const void* B, in
   p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.M = M; p.N = N; p.K = K;
   p.sA = strideA; p.sB = strideB; p.sC = strideC;
   p.drop_ldn = N * drop_row_step; p.drop_base = N * drop_row_off;
-  // big (256x256, LDS-DMA) tiling needs >= 256 rows/cols and 32-bit buffer offsets per operand
-  // (spans include the rows a 256-tile / 64-deep K-tile may address past the end, so the
-  // 32-bit buffer offsets of those out-of-range reads never wrap back into the operand)
-  const int64_t a_span = 2 * (a_kmajor ? (M + 256) * lda : (K + 64) * lda);
-  const int64_t b_span = 2 * (b_kmajor ? (N + 256) * ldb : (K + 64) * ldb);
-  const bool big = M >= 256 && N >= 256 && a_span < (1ll << 32) - 4096 && b_span < (1ll << 32) - 4096;
-  const int tile = big ? 256 : 128;
-  p.tiles_m = (int)((M + tile - 1) / tile);
-  p.tiles_n = (int)((N + tile - 1) / tile);
-  // tile-order group height, measured on the BERT shapes (tools/gemm_bench.py; group-height
-  // sweeps in profiles/r1_gemm_group_sweep.txt): row-major for <= 3 column tiles, 2 with an N-major B (dY.W2), 8 for the
-  // wide forward products (QKV 0.496 -> 0.457 ms, W1+GELU 0.888 -> 0.832 ms)
   int kind = MMU_EPI_STORE;
-  if (epi) kind = epi->kind;
-  // (and 2 for the dGELU product dY2.W2, whose epilogue streams the [M, 3072] gelu' rows:
-  // 0.888 -> 0.756 ms with a K-major B, profiles/r2_gemm_group_dz.txt)
-  p.group_m = p.tiles_n <= 3 ? 1 : ((b_kmajor && kind != MMU_EPI_DGELU) ? 8 : 2);
   if (epi) {
     kind = epi->kind;
     p.accumulate = epi->accumulate;
@@ -260,85 +260,38 @@ static int gemm_impl(const void* A, int64_t lda, int a_kmajor, const void* B, in
     if ((kind == MMU_EPI_STORE_BNB || kind == MMU_EPI_ADD_RES_BNB) && (off16(p.bn_x) || off16(p.bn_mean)))
       return fail("mmu_gemm: bn_x and bn_mean must be 16-B aligned");
   }
-  // split-K for long-K / few-tile products (the weight gradients: K = tokens, M x N = a weight matrix)
-  p.splitk = 1;
-  p.kchunk = K;
-  if (kind == MMU_EPI_STORE && c_dtype == MMU_F32 && !p.bias && !p.colsum && epi && epi->workspace && K >= 1024) {
-    const int64_t tiles = (int64_t)p.tiles_m * p.tiles_n * batch;
-    // slice cap 64 / minimum slice depth 1024 (profiles/r2_splitk_cap_ab.txt); short reductions
-    // (the batch-32 ResNet filter gradients: K = 1.5-25 K pixels over 4-16 tiles) go down to
-    // 256-deep slices so that they still fill the chip
-    const int64_t max_split = 64, min_k = K >= 32768 ? 1024 : 256;
-    int64_t want = (640 + tiles - 1) / tiles;
-    if (want > K / min_k) want = K / min_k;
-    if (want > max_split) want = max_split;
-    const int64_t cap = epi->workspace_floats / (batch * M * N);
-    if (want > cap) want = cap;
-    if (want >= 2) {
-      int64_t chunk = (K + want - 1) / want;
-      chunk = (chunk + 63) / 64 * 64;
-      p.kchunk = chunk;
-      p.splitk = (int)((K + chunk - 1) / chunk);
-      p.ws = epi->workspace;
-    }
-  }
-  // 256 x 384 tiling (gemm_wide_kernel): both operands K-major, N % 384 == 0, no split-K, and at
-  // least MMU_GEMM_WIDE_MIN_TILES of its tiles (default 4 per CU: the bench's M = 131 k rows;
-  // fewer, larger tiles leave CUs idle on small products).  MMU_GEMM_WIDE=0 turns it off.
-  // (read per call, ~1 us: tests switch them inside one process)
-  const char* wide_env = getenv("MMU_GEMM_WIDE");
-  const char* wide_min_env = getenv("MMU_GEMM_WIDE_MIN_TILES");
-  const int wide_mode = wide_env ? atoi(wide_env) : 1;
-  const int64_t wide_min = wide_min_env ? (int64_t)atoll(wide_min_env) : (int64_t)1024;
-  // (the dGELU product stays on 256 x 256: its aux-row loads and column-sum atomics per 64-row
-  // block ran it 15-22 % slower on the wide tile, profiles/r6_gemm_wide_ab.txt)
-  const bool tail_kind = kind == MMU_EPI_STORE || kind == MMU_EPI_BIAS_GELU || kind == MMU_EPI_BIAS_DROP_RES ||
-                         kind == MMU_EPI_DGELU || kind == MMU_EPI_ADD_RES;
-  const bool wide_kind = tail_kind && kind != MMU_EPI_DGELU;
-  // Default rule (MMU_GEMM_WIDE=1), same-box A/B: the wide products N >= 2304 (QKV -3 %, FFN1 + GELU
-  // -8 % with the split tail); N = 768 stays on 256 x 256 (equal or 2 % slower: its 1026 wide tiles
-  // end in a round of 2).  MMU_GEMM_WIDE=2 takes every kind and width (tests).
-  const bool wide = (wide_mode == 2 ? tail_kind : wide_mode == 1 && wide_kind && N >= 2304) && big && a_kmajor &&
-                    b_kmajor && N % 384 == 0 && p.splitk == 1 &&
-                    2 * (M + 256) * lda < (1ll << 32) - 4096 && 2 * (N + 384) * ldb < (1ll << 32) - 4096 &&
-                    (M + 255) / 256 * (N / 384) * batch >= wide_min;
-  if (wide) {
-    p.tiles_m = (int)((M + 255) / 256);
-    p.tiles_n = (int)(N / 384);
-    p.group_m = p.tiles_n <= 2 ? 1 : (kind != MMU_EPI_DGELU ? 8 : 2);
-  }
-  // Split tail rows: when the last round of 256-row tiles holds whole tile rows and is at most an
-  // eighth full (M = 256 x 513 at batch 256: 1026 wide / 1539 big tiles on 256 CUs), those rows
-  // run as split-K partial products of the small tiling into a per-stream f32 scratch, and
-  // splitk_epilogue_kernel sums them and applies the same epilogue.  On by default for the wide
-  // tiling (MMU_GEMM_TAIL=1), whose tail round is 1.5 big tiles long; 2 = for the 256 x 256 tiling
-  // too (tests: there it costs +10-20 us, the 256^2 tail round is short), 0 = off.
-  const char* tail_env = getenv("MMU_GEMM_TAIL");
-  const int tail_mode = tail_env ? atoi(tail_env) : 1;
-  int64_t tail_rows = 0, m_main = M, tail_chunk = K;
-  int tail_split = 1;
-  float* tail_ws = nullptr;
-  if ((tail_mode == 2 || (tail_mode == 1 && wide)) && big && batch == 1 && p.splitk == 1 && tail_kind &&
-      a_kmajor && K >= 512) {
-    const int64_t tiles = (int64_t)p.tiles_m * p.tiles_n, left = tiles % 256;
-    if (tiles > 256 && left > 0 && left % p.tiles_n == 0 && left * 8 <= 256) {
-      m_main = (int64_t)(p.tiles_m - left / p.tiles_n) * 256;
-      tail_rows = M - m_main;
-      const int64_t st = (tail_rows + 127) / 128 * (N / 128);  // small tiles over the tail rows
-      int64_t sk = 256 / st;
-      if (sk > K / 256) sk = K / 256;  // >= 4 K-steps per slice
-      if (sk < 1) sk = 1;
-      tail_chunk = ((K + sk - 1) / sk + 63) / 64 * 64;
-      tail_split = (int)((K + tail_chunk - 1) / tail_chunk);
-      // (a single slice would make the small kernel store its raw product into C: no split then)
-      tail_ws = tail_split >= 2 ? tail_workspace((int64_t)tail_split * tail_rows * N, (hipStream_t)stream) : nullptr;
-      if (!tail_ws) {
-        tail_rows = 0;
-        m_main = M;
-      }
-    }
-  }
+  // ---- plan, assuming both scratch slots can be had; then take only the scratch the plan asks
+  // for, and plan again without a slot that cannot be had (first use under stream capture, a
+  // failed hipMalloc): no tail scratch -> no tail split, no column-sum scratch -> atomics, or the
+  // deterministic refusal
   hipStream_t s = (hipStream_t)stream;
+  const GemmShape shape{M, N, K, batch, lda, ldb, a_kmajor != 0, b_kmajor != 0, c_dtype == MMU_F32, kind,
+                        p.bias != nullptr, p.colsum != nullptr, (epi && epi->workspace) ? epi->workspace_floats : 0};
+  const GemmKnobs knobs = gemm_knobs();
+  GemmScratch scratch{TAIL_WS_FLOATS, TAIL_WS_FLOATS};
+  GemmPlan pl;
+  const char* no = gemm_plan(shape, knobs, scratch, pl);
+  float *tail_ws = nullptr, *cs_part = nullptr;
+  if (!no && pl.tail_rows && !(tail_ws = tail_workspace(pl.tail_split * pl.tail_rows * N, s, 0))) {
+    scratch.tail_floats = 0;
+    no = gemm_plan(shape, knobs, scratch, pl);
+  }
+  if (!no && pl.cs == CS_ROWS && !(cs_part = tail_workspace(pl.cs_parts * N, s, 1))) {
+    scratch.cs_floats = 0;
+    no = gemm_plan(shape, knobs, scratch, pl);
+  }
+  if (no) return refused(no, pl.why);
+  // ---- launch from the plan
+  p.tiles_m = pl.tiles_m; p.tiles_n = pl.tiles_n; p.group_m = pl.group_m;
+  p.splitk = pl.splitk; p.kchunk = pl.kchunk;
+  if (pl.splitk > 1) p.ws = epi->workspace;
+  const int64_t cs_parts_main = pl.cs_parts - (pl.tail_rows + 63) / 64;
+  if (cs_part) {
+    p.cs_part = cs_part;
+    p.cs_m0 = 0;
+    p.cs_rows = pl.cs_rows;
+  }
+  const bool f32out = c_dtype == MMU_F32;
   bool timed;
   std::pair<hipEvent_t, hipEvent_t> ev;
   {
@@ -349,58 +302,39 @@ static int gemm_impl(const void* A, int64_t lda, int a_kmajor, const void* B, in
     ev = take_events();
     (void)hipEventRecord(ev.first, s);
   }
-  // column sums as partial rows (no float atomics: 50 us of the 0.74 ms dZ product at batch 256,
-  // 180 us on the wide tile; profiles/r6_gemm_colsum_ab.txt), folded by one colsum_reduce launch.
-  // Rows of 16 NJ per wave block: 128 on the 256 x 256 tile, 64 on the others.  MMU_GEMM_CS_PART=0: atomics.
-  // Deterministic mode: always the partial rows, whatever MMU_GEMM_CS_PART says; a plain colsum that
-  // cannot take them (batch > 1, no scratch) is refused below instead of reaching the atomics.
-  const bool det = deterministic();
-  const char* csp_env = getenv("MMU_GEMM_CS_PART");
-  const bool cs_plain = p.colsum && kind != MMU_EPI_STORE_STATS && kind != MMU_EPI_STORE_BNB &&
-                        kind != MMU_EPI_ADD_RES_BNB;
-  const bool cs_rows_ok = cs_plain && batch == 1 && p.splitk == 1 && (det || !csp_env || atoi(csp_env) != 0);
-  const int cs_rows_main = (big && !wide) ? 128 : 64;
-  const int64_t cs_parts_main = (m_main + cs_rows_main - 1) / cs_rows_main;
-  const int64_t cs_parts = cs_parts_main + (tail_rows + 63) / 64;
-  float* cs_part = cs_rows_ok ? tail_workspace(cs_parts * N, s, 1) : nullptr;
-  if (det && cs_plain && !cs_part)
-    return fail("mmu_gemm: deterministic mode: colsum with batch=%ld splitk=%d has no partial-row path%s",
-                batch, p.splitk, cs_rows_ok ? " (no scratch: table too large, or first use under stream capture)" : "");
-  if (cs_part) {
-    p.cs_part = cs_part;
-    p.cs_m0 = 0;
-    p.cs_rows = cs_rows_main;
-  }
   {
-    GemmParams pm = p;
-    if (tail_rows) pm.tiles_m = (int)(m_main / 256);
-    if (!(wide && gemm_wide_launch(pm, c_dtype == MMU_F32, (int)batch, s)))
-      gemm_launch(pm, a_kmajor != 0, b_kmajor != 0, c_dtype == MMU_F32, big, (int)batch, s);
+    GemmParams pm = p;  // the main tiling: every tile row, or those above the split tail rows
+    if (pl.tail_rows) pm.tiles_m = (int)(pl.m_main / 256);
+    if (pl.tiling != GEMM_WIDE)
+      gemm_launch(pm, a_kmajor != 0, b_kmajor != 0, f32out, pl.tiling == GEMM_BIG, (int)batch, s);
+    else if (!gemm_wide_launch(pm, f32out, (int)batch, s))
+      return fail("mmu_gemm: internal error: the plan chose the 256 x 384 tiling for epilogue kind %d", kind);
   }
-  if (tail_rows) {
-    GemmParams pt = p;
-    pt.A = p.A + m_main * lda;
-    pt.M = tail_rows;
+  if (pl.tail_rows) {
+    GemmParams pt = p;  // the tail rows' K slices: raw partial products of the small tiling
+    pt.A = p.A + pl.m_main * lda;
+    pt.M = pl.tail_rows;
     pt.kind = MMU_EPI_STORE;
     pt.accumulate = 0;
-    pt.splitk = tail_split;
-    pt.kchunk = tail_chunk;
+    pt.splitk = pl.tail_split;
+    pt.kchunk = pl.tail_chunk;
     pt.ws = tail_ws;
-    pt.tiles_m = (int)((tail_rows + 127) / 128);
+    pt.tiles_m = (int)((pl.tail_rows + 127) / 128);
     pt.tiles_n = (int)(N / 128);
     pt.group_m = 1;
     pt.cs_part = nullptr;
     gemm_launch(pt, true, b_kmajor != 0, true, false, 1, s);
-    GemmParams pe = p;
+    GemmParams pe = p;  // their sum and epilogue
     if (cs_part) {
       pe.cs_part = cs_part + cs_parts_main * N;
-      pe.cs_m0 = m_main;
+      pe.cs_m0 = pl.m_main;
       pe.cs_rows = 64;
     }
-    splitk_epilogue_launch(pe, c_dtype == MMU_F32, tail_ws, m_main, tail_rows, tail_split, s);
+    if (!splitk_epilogue_launch(pe, f32out, tail_ws, pl.m_main, pl.tail_rows, pl.tail_split, s))
+      return fail("mmu_gemm: internal error: the plan split the tail rows of epilogue kind %d", kind);
   }
-  if (cs_part) colsum_reduce_launch(cs_part, cs_parts, N, p.colsum, 1, s);
-  if (p.splitk > 1) splitk_reduce_launch(p, (int)batch, s);
+  if (cs_part) colsum_reduce_launch(cs_part, pl.cs_parts, N, p.colsum, 1, s);
+  if (pl.splitk > 1) splitk_reduce_launch(p, (int)batch, s);
   if (timed) {
     (void)hipEventRecord(ev.second, s);
     std::lock_guard<std::mutex> lk(g_t.mu);
@@ -409,6 +343,27 @@ static int gemm_impl(const void* A, int64_t lda, int a_kmajor, const void* B, in
   }
   return check_launch("mmu_gemm");
 }
+
+// the plan mmu_gemm would follow: the same knobs, through the same plan function, with both scratch
+// slots assumed available; no HIP call
+int mmu_gemm_plan(int64_t M, int64_t N, int64_t K, int64_t batch, int64_t lda, int64_t ldb, int a_kmajor,
+                  int b_kmajor, int c_dtype, int kind, int has_bias, int has_colsum, int64_t workspace_floats,
+                  int64_t* plan) {
+  if (!plan) return fail("mmu_gemm_plan: null plan");
+  if (c_dtype != MMU_BF16 && c_dtype != MMU_F32) return fail("mmu_gemm_plan: bad c_dtype");
+  if (kind < 0 || kind > MMU_EPI_ADD_RES_BNB) return fail("mmu_gemm_plan: bad epilogue kind %d", kind);
+  const GemmShape shape{M, N, K, batch, lda, ldb, a_kmajor != 0, b_kmajor != 0, c_dtype == MMU_F32, kind,
+                        has_bias != 0, has_colsum != 0, workspace_floats};
+  GemmPlan pl;
+  if (const char* no = gemm_plan(shape, gemm_knobs(), GemmScratch{TAIL_WS_FLOATS, TAIL_WS_FLOATS}, pl))
+    return refused(no, pl.why);
+  const int64_t out[MMU_GEMM_PLAN_FIELDS] = {pl.tiling,    pl.tiles_m,    pl.tiles_n, pl.group_m, pl.splitk,
+                                             pl.kchunk,    pl.m_main,     pl.tail_rows, pl.tail_split,
+                                             pl.tail_chunk, pl.cs,        pl.cs_rows, pl.cs_parts};
+  for (int i = 0; i < MMU_GEMM_PLAN_FIELDS; ++i) plan[i] = out[i];
+  return 0;
+}
+
 
 int mmu_gemm(const void* A, int64_t lda, int a_kmajor, const void* B, int64_t ldb, int b_kmajor, void* C,
              int64_t ldc, int c_dtype, int64_t M, int64_t N, int64_t K, int64_t batch, int64_t strideA,
@@ -767,19 +722,17 @@ int mmu_row_pool_bwd(const float* dout, int64_t B, int64_t Hh, int64_t Ww, int64
   return check_launch("mmu_row_pool_bwd");
 }
 
-// conv geometry shared by the gathered conv products: ksize 3 (pad 1) or 1 (pad 0), stride >= 1
-static int conv_geometry(GemmParams& p, int64_t n_img, int64_t H, int64_t W, int64_t C, int64_t ks, int64_t st,
-                         int64_t& Mo, const char* who) {
-  if (n_img <= 0 || H <= 0 || W <= 0 || C <= 0 || (ks != 1 && ks != 3) || st < 1 || st > 4)
-    return fail("%s: bad geometry (n=%ld H=%ld W=%ld C=%ld ksize=%ld stride=%ld)", who, n_img, H, W, C, ks, st);
-  const int64_t pad = ks / 2, Ho = (H + 2 * pad - ks) / st + 1, Wo = (W + 2 * pad - ks) / st + 1;
-  const int64_t in_bytes = 2 * n_img * H * W * C;
-  if (in_bytes >= 0x7FFF0000ll) return fail("%s: input map too large for 32-bit buffer offsets", who);
-  p.conv_h = (int)H; p.conv_w = (int)W; p.conv_c = (int)C;
-  p.conv_ho = (int)Ho; p.conv_wo = (int)Wo; p.conv_ks = (int)ks; p.conv_s = (int)st; p.conv_pad = (int)pad;
-  p.conv_in_bytes = in_bytes;
-  Mo = n_img * Ho * Wo;
-  return 0;
+// the gathered conv products' kernel parameters from their plan (plan.h): ksize 3 (pad 1) or 1 (pad 0)
+static void conv_params(GemmParams& p, const ConvShape& c, const ConvPlan& pl, float* ws) {
+  p.conv_h = (int)c.H; p.conv_w = (int)c.W; p.conv_c = (int)c.C;
+  p.conv_ho = (int)pl.Ho; p.conv_wo = (int)pl.Wo;
+  p.conv_ks = (int)c.ksize; p.conv_s = (int)c.stride; p.conv_pad = (int)(c.ksize / 2);
+  p.conv_in_bytes = pl.in_bytes;
+  p.tiles_m = pl.tiles_m; p.tiles_n = pl.tiles_n;
+  p.group_m = 1;
+  p.splitk = pl.splitk;
+  p.kchunk = pl.kchunk;
+  if (pl.splitk > 1) p.ws = ws;
 }
 
 int mmu_conv_wgrad(const void* dY, const void* X, float* dW, int64_t n_img, int64_t H, int64_t W, int64_t Cin,
@@ -788,41 +741,32 @@ int mmu_conv_wgrad(const void* dY, const void* X, float* dW, int64_t n_img, int6
   if (!dY || !X || !dW) return fail("mmu_conv_wgrad: null pointer");
   if (off16(dY) || off16(X) || off16(dW) || off16(ws))
     return fail("mmu_conv_wgrad: dY, X, dW and the workspace must be 16-B aligned");
-  if (Cin % 256 || Cout % 128 || Cin <= 0 || Cout <= 0)
-    return fail("mmu_conv_wgrad: needs Cin %% 256 == 0, Cout %% 128 == 0 (Cin=%ld Cout=%ld)", Cin, Cout);
-  GemmParams p{};
-  int64_t K;
-  if (conv_geometry(p, n_img, H, W, Cin, ksize, stride, K, "mmu_conv_wgrad")) return 1;
-  if (K >= (1 << 24) || 2 * (K + 64) * Cout >= (1ll << 31))
-    return fail("mmu_conv_wgrad: map too large for 32-bit buffer offsets");
+  const ConvShape c{n_img, H, W, Cin, Cout, ksize, stride, ws ? ws_floats : 0};
+  ConvPlan pl;
+  if (const char* no = conv_wgrad_plan(c, pl)) return refused(no, pl.why);
   const int64_t T = ksize * ksize;
+  GemmParams p{};
   p.A = (const bf16*)dY; p.lda = Cout;  // A = dY^T: M-major [K out pixels][Cout]
   p.B = (const bf16*)X; p.ldb = Cin;    // B gathered: [K out pixels][T Cin]
   p.C = dW; p.ldc = T * Cin;            // dW [Cout][ks][ks][Cin] f32 (channels-last filter)
-  p.M = Cout; p.N = T * Cin; p.K = K;
-  p.tiles_m = (int)((Cout + 255) / 256);
-  p.tiles_n = (int)(T * Cin / 256);
-  p.group_m = 1;
+  p.M = Cout; p.N = T * Cin; p.K = pl.K;
   p.kind = MMU_EPI_STORE;
   p.accumulate = accumulate;
-  // split-K over the pixels (few output tiles): ~640 blocks, >= 1024 pixels per slice
-  const int64_t tiles = (int64_t)p.tiles_m * p.tiles_n;
-  int64_t want = (640 + tiles - 1) / tiles;
-  // (the 2-tile 1x1 downsample, Cin 256 -> Cout 512: up to 128 slices of >= 256 pixels)
-  const bool few = tiles <= 4;
-  if (want > K / (few ? 256 : 1024)) want = K / (few ? 256 : 1024);
-  if (want > (few ? 128 : 32)) want = few ? 128 : 32;
-  if (ws && want > ws_floats / (p.M * p.N)) want = ws_floats / (p.M * p.N);
-  p.splitk = 1;
-  p.kchunk = K;
-  if (ws && want >= 2) {
-    int64_t chunk = ((K + want - 1) / want + 63) / 64 * 64;
-    p.kchunk = chunk;
-    p.splitk = (int)((K + chunk - 1) / chunk);
-    p.ws = ws;
-  }
+  conv_params(p, c, pl, ws);
   conv3x3_wgrad_launch(p, (hipStream_t)stream);
   return check_launch("mmu_conv_wgrad");
+}
+
+int mmu_conv_wgrad_plan(int64_t n_img, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int64_t ksize,
+                        int64_t stride, int64_t ws_floats, int64_t* plan) {
+  if (!plan) return fail("mmu_conv_wgrad_plan: null plan");
+  ConvPlan pl;
+  if (const char* no = conv_wgrad_plan(ConvShape{n_img, H, W, Cin, Cout, ksize, stride, ws_floats}, pl))
+    return refused(no, pl.why);
+  const int64_t out[MMU_CONV_WGRAD_PLAN_FIELDS] = {pl.K,       pl.Ho,  pl.Wo,     pl.tiles_m,
+                                                   pl.tiles_n, pl.few, pl.splitk, pl.kchunk};
+  for (int i = 0; i < MMU_CONV_WGRAD_PLAN_FIELDS; ++i) plan[i] = out[i];
+  return 0;
 }
 
 int mmu_conv3x3_wgrad(const void* dY, const void* X, float* dW, int64_t n_img, int64_t H, int64_t W, int64_t Cin,
@@ -878,46 +822,33 @@ static int conv_implicit(const void* X, const void* Wk, void* Y, int64_t n_img, 
   // (bn_mask is read by the byte)
   if (off16(X) || off16(Wk) || off16(Y) || off16(stats) || off16(ws) || off16(bn_x) || off16(bn_mean))
     return fail("mmu_conv_implicit: X, Wk, Y, the table, the workspace, bn_x and bn_mean must be 16-B aligned");
-  if (C % 64 || N % 64 || N <= 0)
-    return fail("mmu_conv_implicit: needs C %% 64 == 0, N %% 64 == 0 (C=%ld N=%ld)", C, N);
-  GemmParams p{};
-  int64_t M;
-  if (conv_geometry(p, n_img, H, W, C, ksize, stride, M, "mmu_conv_implicit")) return 1;
+  const ConvShape c{n_img, H, W, C, N, ksize, stride, ws ? ws_floats : 0};
+  ConvPlan pl;
+  if (const char* no = conv_implicit_plan(c, pl)) return refused(no, pl.why);
   const int64_t T = ksize * ksize;
-  if (M < 256 || 2 * (M + 256) * N >= (1ll << 31) || 2 * (N + 256) * T * C >= (1ll << 31))
-    return fail("mmu_conv_implicit: map size out of range");
-  // 256x256 tiles (LDS-DMA gather) for N >= 256 with N % 128 == 0; 128x128 register-staged
-  // tiles for the narrow convs (N = 64 / 128 / ...)
-  const bool small = N < 256 || N % 128;
-  const int tm_ = small ? 128 : 256, tn_ = small ? 128 : 256;
+  GemmParams p{};
   p.A = (const bf16*)X; p.lda = C;       // A gathered: [M out pixels][T C]
   p.B = (const bf16*)Wk; p.ldb = T * C;  // B K-major [N][T C]
   p.C = Y; p.ldc = N;                    // Y [M pixels][N] bf16
-  p.M = M; p.N = N; p.K = T * C;
-  p.tiles_m = (int)((M + tm_ - 1) / tm_);
-  p.tiles_n = (int)((N + tn_ - 1) / tn_);
-  p.group_m = 1;
+  p.M = pl.pixels; p.N = N; p.K = pl.K;
   p.kind = !stats ? MMU_EPI_STORE : bn_x ? MMU_EPI_STORE_BNB : MMU_EPI_STORE_STATS;
   p.colsum = stats;
   p.bn_x = (const bf16*)bn_x; p.bn_mask = bn_mask; p.bn_mean = bn_mean;
-  p.splitk = 1;
-  p.kchunk = p.K;
-  // split K (taps x channels) when the map has fewer tiles than half the CUs: ~512 blocks, >= 4
-  // 64-deep steps per slice, slabs bounded by the workspace
-  const int64_t tiles = (int64_t)p.tiles_m * p.tiles_n;
-  if (ws && tiles < 128) {
-    int64_t want = (512 + tiles - 1) / tiles;
-    if (want > p.K / 256) want = p.K / 256;
-    if (want > ws_floats / (M * N)) want = ws_floats / (M * N);
-    if (want >= 2) {
-      const int64_t chunk = ((p.K + want - 1) / want + 63) / 64 * 64;
-      p.kchunk = chunk;
-      p.splitk = (int)((p.K + chunk - 1) / chunk);
-      p.ws = ws;
-    }
-  }
-  conv3x3_implicit_launch(p, small, (hipStream_t)stream);
+  conv_params(p, c, pl, ws);
+  conv3x3_implicit_launch(p, pl.small, (hipStream_t)stream);
   return check_launch("mmu_conv_implicit");
+}
+
+int mmu_conv_implicit_plan(int64_t n_img, int64_t H, int64_t W, int64_t C, int64_t N, int64_t ksize, int64_t stride,
+                           int64_t ws_floats, int64_t* plan) {
+  if (!plan) return fail("mmu_conv_implicit_plan: null plan");
+  ConvPlan pl;
+  if (const char* no = conv_implicit_plan(ConvShape{n_img, H, W, C, N, ksize, stride, ws_floats}, pl))
+    return refused(no, pl.why);
+  const int64_t out[MMU_CONV_IMPLICIT_PLAN_FIELDS] = {pl.small,   pl.pixels, pl.K,      pl.Ho, pl.Wo,
+                                                      pl.tiles_m, pl.tiles_n, pl.splitk, pl.kchunk};
+  for (int i = 0; i < MMU_CONV_IMPLICIT_PLAN_FIELDS; ++i) plan[i] = out[i];
+  return 0;
 }
 
 int mmu_conv_implicit(const void* X, const void* Wk, void* Y, int64_t n_img, int64_t H, int64_t W, int64_t C,
@@ -946,8 +877,20 @@ int mmu_conv3x3_implicit_bnb(const void* X, const void* Wk, void* Y, int64_t n_i
 
 int64_t mmu_batchnorm_ws_bytes(int64_t C) { return batchnorm_ws_bytes(C); }
 
-static int bn_common(int64_t rows, int64_t C, void* ws, int64_t ws_bytes, const char* who) {
+static int bn_shape(int64_t rows, int64_t C, const char* who) {
   if (rows <= 0 || C <= 0 || C % 8 || C > 2048) return fail("%s: C=%ld must be a multiple of 8, <= 2048", who, C);
+  return 0;
+}
+
+int mmu_batchnorm_plan(int64_t rows, int64_t C, int64_t* plan) {
+  if (!plan) return fail("mmu_batchnorm_plan: null plan");
+  if (bn_shape(rows, C, "mmu_batchnorm_plan")) return 1;
+  batchnorm_plan(rows, C, plan);
+  return 0;
+}
+
+static int bn_common(int64_t rows, int64_t C, void* ws, int64_t ws_bytes, const char* who) {
+  if (bn_shape(rows, C, who)) return 1;
   if (!ws || ws_bytes < batchnorm_ws_bytes(C) || ((uintptr_t)ws & 15))
     return fail("%s: ws must be >= mmu_batchnorm_ws_bytes(C) bytes, 16-B aligned", who);
   return 0;

@@ -241,6 +241,8 @@ struct BnBwdParams {
 };
 void batchnorm_bwd_launch(const BnBwdParams& q, hipStream_t s);
 int64_t batchnorm_ws_bytes(int64_t C);
+// bn_grid's choice for a [rows, C] map, in the field order of mmu_batchnorm_plan (include/mmu.h)
+void batchnorm_plan(int64_t rows, int64_t C, int64_t plan[MMU_BATCHNORM_PLAN_FIELDS]);
 
 void uncertainty_launch(const float* logits, const int64_t* y, int64_t S, int64_t R, int64_t C, float* p_bar,
                         float* nll, float* conf, float* correct, hipStream_t s);

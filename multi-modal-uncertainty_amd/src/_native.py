@@ -117,10 +117,26 @@ SIGNATURES = {
                                           c_vp, c_vp]),
     "mmu_robustness_summary": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp,
                                        c_vp]),
+    "mmu_gemm_plan": (c_i32, [c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64,
+                              c_i64p]),
+    "mmu_conv_implicit_plan": (c_i32, [c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64p]),
+    "mmu_conv_wgrad_plan": (c_i32, [c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64p]),
+    "mmu_batchnorm_plan": (c_i32, [c_i64, c_i64, c_i64p]),
     "mmu_timing_enable": (c_i32, [c_i32]),
     "mmu_timing_pause": (c_i32, [c_i32]),
     "mmu_timing_read": (c_i32, [c_dp, c_i64p, c_dp]),
 }
+
+# the int64 fields each mmu_*_plan query fills, in order (include/mmu.h, MMU_*_PLAN_FIELDS of them)
+PLAN_FIELDS = {
+    "mmu_gemm_plan": ("tiling", "tiles_m", "tiles_n", "group_m", "splitk", "kchunk", "m_main", "tail_rows",
+                      "tail_split", "tail_chunk", "cs", "cs_rows", "cs_parts"),
+    "mmu_conv_implicit_plan": ("small", "M", "K", "Ho", "Wo", "tiles_m", "tiles_n", "splitk", "kchunk"),
+    "mmu_conv_wgrad_plan": ("K", "Ho", "Wo", "tiles_m", "tiles_n", "few", "splitk", "kchunk"),
+    "mmu_batchnorm_plan": ("CH", "rpi", "rpb", "blocks", "gy", "clamped"),
+}
+GEMM_TILINGS = ("small", "big", "wide")             # mmu_gemm_plan's tiling: 128^2, 256^2, 256 x 384
+GEMM_COLSUMS = ("none", "atomics", "rows", "table")  # and its cs
 
 _lib = None
 

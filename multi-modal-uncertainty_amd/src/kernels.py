@@ -201,6 +201,40 @@ def _splitk_workspace(dev):
     return t
 
 
+# ---- launch plans: what the host would choose, asked of the library itself (no launch, no GPU needed)
+def _plan(name, *args):
+    out = (ctypes.c_int64 * len(N.PLAN_FIELDS[name]))()
+    N.call(name, *args, out)
+    return dict(zip(N.PLAN_FIELDS[name], out))
+
+
+def gemm_plan(M, N_, K, batch=1, lda=None, ldb=None, a_kmajor=True, b_kmajor=True, c_f32=False, kind=EPI_STORE,
+              bias=False, colsum=False, ws_floats=SPLITK_WS_FLOATS):
+    """mmu_gemm_plan (include/mmu.h) -> dict of its fields, "tiling" and "cs" by name: the plan of
+    gemm() for this shape under the MMU_GEMM_* environment and the deterministic switch as they
+    stand.  lda / ldb default to dense operands; ws_floats to the workspace gemm() passes."""
+    d = _plan("mmu_gemm_plan", M, N_, K, batch, lda or (K if a_kmajor else M), ldb or (K if b_kmajor else N_),
+              int(a_kmajor), int(b_kmajor), N.MMU_F32 if c_f32 else N.MMU_BF16, kind, int(bool(bias)),
+              int(bool(colsum)), ws_floats)
+    d["tiling"], d["cs"] = N.GEMM_TILINGS[d["tiling"]], N.GEMM_COLSUMS[d["cs"]]
+    return d
+
+
+def conv_plan(n, H, W, C, N_, ksize=3, stride=1, ws_floats=SPLITK_WS_FLOATS):
+    """mmu_conv_implicit_plan -> dict: the plan of conv_implicit() / conv3x3_implicit()"""
+    return _plan("mmu_conv_implicit_plan", n, H, W, C, N_, ksize, stride, ws_floats)
+
+
+def conv_wgrad_plan(n, H, W, Cin, Cout, ksize=3, stride=1, ws_floats=SPLITK_WS_FLOATS):
+    """mmu_conv_wgrad_plan -> dict: the plan of conv_wgrad() / conv3x3_wgrad()"""
+    return _plan("mmu_conv_wgrad_plan", n, H, W, Cin, Cout, ksize, stride, ws_floats)
+
+
+def batchnorm_plan(rows, C):
+    """mmu_batchnorm_plan -> dict: the row-block grid of the batchnorm_* passes over a [rows, C] map"""
+    return _plan("mmu_batchnorm_plan", rows, C)
+
+
 SIDE_CU_FRAC = None  # e.g. 0.75: the side stream's kernels run on that fraction of every XCD's CUs
 
 

@@ -27,15 +27,15 @@ kernels: mask_bits / mask_bools convert); a stream residue [rows, C] int8.
                    mean |x| / mean x^2 n / (n - 1)
         invstd     invstd
 
-bn_geometry restates bn_grid (csrc/batchnorm.hip:396-411).  It chooses the row counts of the sweep
-(bn_rows), the two rows the "tail" inputs make large, and the block split of the model's partial
-sums; the dense list BN_DENSE does not depend on it.
+bn_geometry asks the host for bn_grid's choice (mmu_batchnorm_plan; the built library, no GPU).  It
+chooses the row counts of the sweep (bn_rows), the two rows the "tail" inputs make large, and the
+block split of the model's partial sums; the dense list BN_DENSE does not depend on it.
 """
 import torch
 
 from rowops_harness import bf16r, check_bf16
+from src import kernels
 
-BN_THREADS = 256
 BN_EPS = 1e-5
 RES_BAR = 2.0 ** -13   # the decoded stream against the f32 value (test_batchnorm_stream_residue's bar)
 RES_ROUNDTRIP = 2.0 ** -15
@@ -49,23 +49,12 @@ def eps32(eps=BN_EPS):
 
 # ------------------------------------------------------------------------------- geometry
 def bn_geometry(rows, C):
-    """bn_grid restated (csrc/batchnorm.hip:396-411; tpr / rpi as bn_geom, :47-57) ->
-    {"CH", "tpr", "rpi", "rpb", "blocks" (grid.x = nparts), "gy" (grid.y), "clamped"}"""
-    CH = 512
-    while C % CH:
-        CH >>= 1
-    tpr = CH // 8
-    rpi = BN_THREADS // tpr
-    per = rows * C // 1024
-    per = 8192 if per < 8192 else 65536 if per > 65536 else per
-    rpb = (per + CH - 1) // CH
-    rpb = (rpb + rpi - 1) // rpi * rpi
-    max_parts = (1 << 20) // C
-    clamped = (rows + rpb - 1) // rpb > max_parts
-    if clamped:
-        rpb = ((rows + max_parts - 1) // max_parts + rpi - 1) // rpi * rpi
-    return {"CH": CH, "tpr": tpr, "rpi": rpi, "rpb": rpb, "blocks": (rows + rpb - 1) // rpb, "gy": C // CH,
-            "clamped": clamped}
+    """the host's own row-block grid for a [rows, C] map (kernels.batchnorm_plan: mmu_batchnorm_plan
+    reports bn_grid of csrc/batchnorm.hip) -> {"CH", "rpi", "rpb", "blocks" (grid.x = nparts), "gy"
+    (grid.y), "clamped"} and the label "tpr": the threads that share a row"""
+    g = kernels.batchnorm_plan(rows, C)
+    g.update(tpr=g["CH"] // 8, clamped=bool(g["clamped"]))
+    return g
 
 
 BN_C = (8, 24, 64, 96, 256, 520, 2048)      # CH = 8, 8 x 3, 64, 32 x 3, 256, 8 x 65, 512 x 4

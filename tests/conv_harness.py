@@ -26,9 +26,10 @@ the STATS / BNB tables are table_ref / table_model over the kernel's own stored 
                    element seeds -> values and the 0..8 window position
   row_pool_ref / row_pool_model   AdaptiveAvgPool2d((n, 1)): bins [floor(i Hh / n), ceil((i + 1) Hh / n))
 
-conv_plan / wgrad_plan RESTATE conv_implicit / mmu_conv_wgrad of csrc/capi.hip (small or big kernel,
-tiles, splitk, kchunk, few / many).  As with gemm_plan they only label the cases and hand the
-summation order to the f32 model: whether a result is right never depends on them.
+conv_plan / wgrad_plan ASK the host for its plan (mmu_conv_implicit_plan / mmu_conv_wgrad_plan: the
+plan functions of csrc/plan.h that the launches themselves run -- small or big kernel, tiles, splitk,
+kchunk, few / many; the built library, no GPU).  As with gemm_plan they label the cases and hand the
+summation order to the f32 model.
 
 Input kinds: "int" X, dY in -3..3 and W in -2..2: |product| <= 9, and 9 K < 2^24 for every case, so
 every f32 partial sum is exact in any order; "gauss" X, dY ~ N(0, 1), W ~ 0.1 N(0, 1).
@@ -37,8 +38,10 @@ import torch
 
 import gemm_harness as G
 
+from src import kernels
+
 bf16 = torch.bfloat16
-SPLITK_WS_FLOATS = G.SPLITK_WS_FLOATS
+SPLITK_WS_FLOATS = kernels.SPLITK_WS_FLOATS
 
 
 def conv_out(h, w, ks, stride):
@@ -136,45 +139,30 @@ def int_sum_bound(c):
 
 
 # ------------------------------------------------------------------------------- the host's plans
+def _slices(p):
+    """the K depth of every slice of a queried plan"""
+    return [min(p["kchunk"], p["K"] - i * p["kchunk"]) for i in range(p["splitk"])]
+
+
 def conv_plan(n, H, W, C, N, ks, stride, ws_floats=SPLITK_WS_FLOATS):
-    """restatement of conv_implicit (csrc/capi.hip) -> dict kernel "small" | "big", M, K, tiles_m,
-    tiles_n, tiles, splitk, kchunk, slices (the K depth of every slice), split ("unsplit" |
-    "split-even" | "split-uneven")"""
-    Ho, Wo = conv_out(H, W, ks, stride)
-    M, K = n * Ho * Wo, ks * ks * C
-    small = N < 256 or N % 128 != 0
-    t = 128 if small else 256
-    tiles_m, tiles_n = (M + t - 1) // t, (N + t - 1) // t
-    tiles = tiles_m * tiles_n
-    splitk, kchunk = 1, K
-    if tiles < 128:
-        want = min((512 + tiles - 1) // tiles, K // 256, ws_floats // (M * N))
-        if want >= 2:
-            kchunk = ((K + want - 1) // want + 63) // 64 * 64
-            splitk = (K + kchunk - 1) // kchunk
-    slices = [min(kchunk, K - i * kchunk) for i in range(splitk)]
-    split = "unsplit" if splitk == 1 else "split-even" if slices[-1] == kchunk else "split-uneven"
-    return dict(kernel="small" if small else "big", M=M, K=K, Ho=Ho, Wo=Wo, tiles_m=tiles_m, tiles_n=tiles_n,
-                tiles=tiles, splitk=splitk, kchunk=kchunk, slices=slices, split=split)
+    """the host's plan for the forward / data-gradient product (kernels.conv_plan:
+    mmu_conv_implicit_plan runs the function mmu_conv_implicit runs) -> its dict M, K, Ho, Wo, tiles_m,
+    tiles_n, splitk, kchunk, and the labels kernel "small" | "big", tiles, slices (the K depth of
+    every slice), split ("unsplit" | "split-even" | "split-uneven")"""
+    p = kernels.conv_plan(n, H, W, C, N, ks, stride, ws_floats)
+    p.update(kernel="small" if p["small"] else "big", tiles=p["tiles_m"] * p["tiles_n"], slices=_slices(p))
+    p["split"] = "unsplit" if p["splitk"] == 1 else "split-even" if p["slices"][-1] == p["kchunk"] else "split-uneven"
+    return p
 
 
 def wgrad_plan(n, H, W, Cin, Cout, ks, stride, ws_floats=SPLITK_WS_FLOATS):
-    """restatement of mmu_conv_wgrad (csrc/capi.hip) -> dict K (output pixels), tiles_m, tiles_n, tiles,
-    few, splitk, kchunk, slices, path ("few-unsplit" | "few-split" | "many-unsplit" | "many-split")"""
-    Ho, Wo = conv_out(H, W, ks, stride)
-    K, T = n * Ho * Wo, ks * ks
-    tiles_m, tiles_n = (Cout + 255) // 256, T * Cin // 256
-    tiles = tiles_m * tiles_n
-    few = tiles <= 4
-    want = min((640 + tiles - 1) // tiles, K // (256 if few else 1024), 128 if few else 32,
-               ws_floats // (Cout * T * Cin))
-    splitk, kchunk = 1, K
-    if want >= 2:
-        kchunk = ((K + want - 1) // want + 63) // 64 * 64
-        splitk = (K + kchunk - 1) // kchunk
-    slices = [min(kchunk, K - i * kchunk) for i in range(splitk)]
-    return dict(K=K, Ho=Ho, Wo=Wo, tiles_m=tiles_m, tiles_n=tiles_n, tiles=tiles, few=few, splitk=splitk, kchunk=kchunk,
-                slices=slices, path=("few" if few else "many") + ("-unsplit" if splitk == 1 else "-split"))
+    """the host's plan for the weight gradient (kernels.conv_wgrad_plan: mmu_conv_wgrad_plan) -> its
+    dict K (output pixels), Ho, Wo, tiles_m, tiles_n, few, splitk, kchunk, and the labels tiles,
+    slices, path ("few-unsplit" | "few-split" | "many-unsplit" | "many-split")"""
+    p = kernels.conv_wgrad_plan(n, H, W, Cin, Cout, ks, stride, ws_floats)
+    p.update(few=bool(p["few"]), tiles=p["tiles_m"] * p["tiles_n"], slices=_slices(p))
+    p["path"] = ("few" if p["few"] else "many") + ("-unsplit" if p["splitk"] == 1 else "-split")
+    return p
 
 
 # ------------------------------------------------------------------------------- the sweep's cases

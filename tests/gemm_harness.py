@@ -36,13 +36,17 @@ against the model) for bf16 outputs, check_f32 (8 x the model's error or 4 ulps)
 "int" inputs make every partial sum exact in f32 in any order, so an f32 C must equal the reference
 bit for bit.
 
-gemm_plan RESTATES the host's choice of tiling, tile order, split-K, split tail and column-sum path
-(csrc/capi.hip, gemm_impl).  It is a restatement and can drift from the host: it only chooses and
-labels the cases (test_gemm_reference.py asserts that every path has cases); whether a result is
-right never depends on it, except through the summation order handed to gemm_model32 for f32 bars.
+gemm_plan ASKS the host for its choice of tiling, tile order, split-K, split tail and column-sum
+path (mmu_gemm_plan: the plan function of csrc/plan.h that mmu_gemm itself runs; it needs the built
+library but no GPU).  The plan chooses and labels the cases (test_gemm_reference.py asserts that
+every path has cases) and hands gemm_model32 the summation order the f32 bars rest on.
 """
+import os
+
 import numpy as np
 import torch
+
+from src import kernels
 
 bf16 = torch.bfloat16
 (STORE, BIAS_GELU, BIAS_DROP_RES, DGELU, ADD_RES, BIAS_DROP_QGELU, STORE_STATS, STORE_BNB, ADD_RES_BNB) = range(9)
@@ -303,78 +307,31 @@ def table_model(Cst, kind, e):
 
 
 # ------------------------------------------------------------------------------- the host's plan
-SPLITK_WS_FLOATS = 16 << 20   # src/kernels.py: the per-stream workspace every call is given
-TAIL_WS_FLOATS = 8 << 20      # csrc/capi.hip:90
-
-
-def gemm_plan(M, N, K, batch, a_kmajor, b_kmajor, kind, c_f32, has_ws, env=None, lda=None, ldb=None, bias=False,
-              colsum=False, ws_floats=SPLITK_WS_FLOATS, det=False):
-    """restatement of gemm_impl's choices (csrc/capi.hip; line numbers as of this sweep) -> dict
-    tiling "small" (128^2) | "big" (256^2) | "wide" (256 x 384), tiles_m, tiles_n, group_m, splitk,
-    kchunk, tail_rows, tail_split, tail_chunk, m_main, cs ("none" | "rows" | "atomics" | "table").
-    A restatement: it can drift from the host (module docstring)."""
-    env = env or {}
-    lda = lda or (K if a_kmajor else M)
-    ldb = ldb or (K if b_kmajor else N)
-    lim = (1 << 32) - 4096
-    a_span = 2 * ((M + 256) * lda if a_kmajor else (K + 64) * lda)          # capi.hip:169-170
-    b_span = 2 * ((N + 256) * ldb if b_kmajor else (K + 64) * ldb)
-    big = M >= 256 and N >= 256 and a_span < lim and b_span < lim            # :171
-    tile = 256 if big else 128
-    tiles_m, tiles_n = (M + tile - 1) // tile, (N + tile - 1) // tile        # :173-174
-    group_m = 1 if tiles_n <= 3 else (8 if (b_kmajor and kind != DGELU) else 2)  # :182
-    splitk, kchunk = 1, K
-    if kind == STORE and c_f32 and not bias and not colsum and has_ws and K >= 1024:   # :262
-        tiles = tiles_m * tiles_n * batch
-        min_k = 1024 if K >= 32768 else 256                                  # :267
-        want = min((640 + tiles - 1) // tiles, K // min_k, 64, ws_floats // (batch * M * N))  # :268-272
-        if want >= 2:
-            kchunk = ((K + want - 1) // want + 63) // 64 * 64                # :274-275
-            splitk = (K + kchunk - 1) // kchunk
-    wide_mode = int(env.get("MMU_GEMM_WIDE", 1))                            # :285-288
-    wide_min = int(env.get("MMU_GEMM_WIDE_MIN_TILES", 1024))
-    tail_kind = kind in (STORE, BIAS_GELU, BIAS_DROP_RES, DGELU, ADD_RES)   # :291-293
-    wide_kind = tail_kind and kind != DGELU
-    wide = ((tail_kind if wide_mode == 2 else (wide_mode == 1 and wide_kind and N >= 2304)) and big and a_kmajor
-            and b_kmajor and N % 384 == 0 and splitk == 1 and 2 * (M + 256) * lda < lim
-            and 2 * (N + 384) * ldb < lim and (M + 255) // 256 * (N // 384) * batch >= wide_min)  # :297-300
-    if wide:
-        tiles_m, tiles_n = (M + 255) // 256, N // 384                        # :302-304
-        group_m = 1 if tiles_n <= 2 else (8 if kind != DGELU else 2)
-    tail_mode = int(env.get("MMU_GEMM_TAIL", 1))                            # :312-313
-    tail_rows, m_main, tail_chunk, tail_split = 0, M, K, 1
-    if ((tail_mode == 2 or (tail_mode == 1 and wide)) and big and batch == 1 and splitk == 1 and tail_kind
-            and a_kmajor and K >= 512):                                      # :317-318
-        tiles = tiles_m * tiles_n
-        left = tiles % 256
-        if tiles > 256 and left > 0 and left % tiles_n == 0 and left * 8 <= 256:   # :320
-            m_main = (tiles_m - left // tiles_n) * 256
-            tail_rows = M - m_main
-            st = (tail_rows + 127) // 128 * (N // 128)
-            sk = max(1, min(256 // st, K // 256))                            # :324-326
-            tail_chunk = ((K + sk - 1) // sk + 63) // 64 * 64
-            tail_split = (K + tail_chunk - 1) // tail_chunk
-            if tail_split < 2 or tail_split * tail_rows * N > TAIL_WS_FLOATS:   # :330-334, :95
-                tail_rows, m_main, tail_split, tail_chunk = 0, M, 1, K
-    cs = "none"
-    if colsum:
-        if kind in (STORE_STATS, STORE_BNB, ADD_RES_BNB):
-            cs = "table"
-        else:                                                                # :355-361
-            cs_rows = 128 if (big and not wide) else 64
-            parts = (m_main + cs_rows - 1) // cs_rows + (tail_rows + 63) // 64
-            rows_ok = batch == 1 and splitk == 1 and (det or int(env.get("MMU_GEMM_CS_PART", 1)) != 0)
-            cs = "rows" if rows_ok and parts * N <= TAIL_WS_FLOATS else "atomics"
-    return dict(tiling="wide" if wide else "big" if big else "small", tiles_m=tiles_m, tiles_n=tiles_n,
-                group_m=group_m, splitk=splitk, kchunk=kchunk, tail_rows=tail_rows, tail_split=tail_split,
-                tail_chunk=tail_chunk, m_main=m_main, cs=cs,
-                wgs=(m_main // 256 if tail_rows else tiles_m) * tiles_n * splitk * batch)
+def gemm_plan(M, N, K, batch, a_kmajor, b_kmajor, kind, c_f32, env=None, lda=None, ldb=None, bias=False,
+              colsum=False, ws_floats=kernels.SPLITK_WS_FLOATS):
+    """the host's own plan for the product (kernels.gemm_plan: mmu_gemm_plan runs the function
+    mmu_gemm runs), queried under the MMU_GEMM_* variables of `env` -> its dict: tiling ("small"
+    128^2 | "big" 256^2 | "wide" 256 x 384), tiles_m, tiles_n, group_m, splitk, kchunk, m_main,
+    tail_rows, tail_split, tail_chunk, cs ("none" | "atomics" | "rows" | "table"), cs_rows, cs_parts,
+    and the label wgs: the workgroups of the main launch.  ws_floats: by default the wrapper's workspace."""
+    saved = {k: os.environ.pop(k, None) for k in ENV_KEYS}
+    os.environ.update(env or {})
+    try:
+        pl = kernels.gemm_plan(M, N, K, batch, lda, ldb, a_kmajor, b_kmajor, c_f32, kind, bias, colsum, ws_floats)
+    finally:
+        for k, v in saved.items():
+            os.environ.pop(k, None)
+            if v is not None:
+                os.environ[k] = v
+    pl["wgs"] = (pl["m_main"] // 256 if pl["tail_rows"] else pl["tiles_m"]) * pl["tiles_n"] * pl["splitk"] * batch
+    return pl
 
 
 # ------------------------------------------------------------------------------- the sweep's cases
 WIDE_ENV = {"MMU_GEMM_WIDE": "2", "MMU_GEMM_WIDE_MIN_TILES": "1"}
 TAIL_ENV = {"MMU_GEMM_TAIL": "2"}
 ATOMICS_ENV = {"MMU_GEMM_CS_PART": "0"}
+ENV_KEYS = ("MMU_GEMM_WIDE", "MMU_GEMM_WIDE_MIN_TILES", "MMU_GEMM_TAIL", "MMU_GEMM_CS_PART")
 SMALL_M = (1, 7, 8, 9, 15, 16, 17, 63, 64, 65, 127, 128, 129, 191, 193, 255)
 BIG_M = (256, 257, 263, 264, 319, 320, 321, 383, 384, 385, 511, 513)
 WIDE_M = (256, 257, 320, 321, 511, 513)
@@ -409,9 +366,10 @@ def pad_of(c):
 
 
 def plan_of(c):
-    ws = SPLITK_WS_FLOATS if c["ws_slices"] is None else c["ws_slices"] * c["batch"] * c["M"] * c["N"]
+    """the host's plan for the case, queried under the case's own MMU_GEMM_* variables"""
+    ws = kernels.SPLITK_WS_FLOATS if c["ws_slices"] is None else c["ws_slices"] * c["batch"] * c["M"] * c["N"]
     pad = pad_of(c)
-    return gemm_plan(c["M"], c["N"], c["K"], c["batch"], c["ak"], c["bk"], c["kind"], c["c_f32"], True, c["env"],
+    return gemm_plan(c["M"], c["N"], c["K"], c["batch"], c["ak"], c["bk"], c["kind"], c["c_f32"], c["env"],
                      lda=(c["K"] if c["ak"] else c["M"]) + pad, ldb=(c["K"] if c["bk"] else c["N"]) + pad,
                      bias=c["bias"] and c["kind"] not in (DGELU, ADD_RES, STORE_BNB, ADD_RES_BNB),
                      colsum=c["colsum"] or c["kind"] >= STORE_STATS, ws_floats=ws)

@@ -180,6 +180,10 @@ def run_case(k, dev, mp, c, seed, fails, log, worst):
     ws_buf = outs.pop("workspace", None)
     if ws_buf is not None and not ws_buf.guards_intact():
         fails.append(f"{tag}: wrote outside the caller's workspace")
+    if ws_buf is not None:      # ("int" inputs: every slab element is finite) the launch followed the queried plan
+        used, slabs = int(torch.isfinite(ws_buf.view).sum()), pl["splitk"] * batch * M * N if pl["splitk"] > 1 else 0
+        if used != slabs:
+            fails.append(f"{tag}: {used} workspace floats written, the queried plan ({pl['splitk']} slices) has {slabs}")
     check_written(outs, fails, tag)
     for name, g in ins.items():
         if not g.unchanged():
