@@ -307,10 +307,18 @@ int mmu_layernorm_bwd_res(const void* dY, const void* X, const float* mean, cons
  * output, row s*N + n, q at col h*D, k at E + h*D, v at 2E + h*D (E = heads*D).
  * softmax(Q K^T / sqrt(D)) V per (n, h); no mask, no dropout (module defaults).
  *   O [S*N, ld_o] bf16 (col h*D); LSE2 [N*heads, S] f32 = log2-sum-exp2 of the scores
- *   scaled by log2(e)/sqrt(D) (for the backward).  D in {64, 128, 256}. */
+ *   scaled by log2(e)/sqrt(D) (for the backward).  D in {64, 128, 256}.
+ * Refused (nonzero return, mmu_last_error): a null pointer; S, N or heads <= 0; another D;
+ * ld_qkv < 3E or not a multiple of 8; ld_o < E or not a multiple of 4; N*heads > 65535;
+ * S > INT32_MAX - 63 (rows and 64-row tiles are counted in int); QKV not 16-byte, O not 8-byte,
+ * LSE2 not 4-byte aligned (16-B row loads, 8-B row stores). */
 int mmu_seqattn_fwd(const void* QKV, int64_t ld_qkv, void* O, int64_t ld_o, float* LSE2,
                     int64_t S, int64_t N, int64_t heads, int64_t head_dim, mmu_stream_t stream);
-/* dQKV [S*N, ld_dqkv] bf16 (every element written); delta workspace [N*heads, S] f32. */
+/* dQKV [S*N, ld_dqkv] bf16 (every element written); delta workspace [N*heads, S] f32.
+ * Refused: what the forward refuses of QKV, S, N, heads and D; ld_dqkv < 3E or not a multiple of
+ * 4; ld_o < E or not a multiple of 4; ld_do < E or not a multiple of 8; QKV or dO not 16-byte,
+ * O or dQKV not 8-byte, LSE2 or delta not 4-byte aligned; more than INT32_MAX delta blocks
+ * (ceil(S*N*heads / 4), the x dimension of one grid). */
 int mmu_seqattn_bwd(const void* QKV, int64_t ld_qkv, const void* O, int64_t ld_o,
                     const void* dO, int64_t ld_do, const float* LSE2, float* delta,
                     void* dQKV, int64_t ld_dqkv, int64_t S, int64_t N, int64_t heads,

@@ -585,6 +585,17 @@ static int seqattn_check(const char* what, int64_t ld_qkv, int64_t S, int64_t N,
   if (D != 64 && D != 128 && D != 256) return fail("%s: head_dim %ld not in {64, 128, 256}", what, D);
   if (ld_qkv < 3 * heads * D || ld_qkv % 8) return fail("%s: ld_qkv too small / unaligned", what);
   if (N * heads > 65535) return fail("%s: N*heads > 65535", what);
+  // the kernels count rows and 64-row tiles in int: the last tile's end, ceil(S/64)*64, must fit
+  if (S > (int64_t)INT32_MAX - 63)
+    return fail("%s: S = %ld exceeds %ld (INT32_MAX - 63: rows and 64-row tiles are counted in int)", what, S,
+                (int64_t)INT32_MAX - 63);
+  return 0;
+}
+
+// the 16-B row loads (QKV, dO), 8-B row stores (O, dQKV) and f32 vectors (LSE2, delta) of flava.hip
+static int seqattn_aligned(const char* what, const char* name, const void* q, int bytes) {
+  if ((uintptr_t)q & (uintptr_t)(bytes - 1))
+    return fail("%s: %s = %p must be %d-byte aligned", what, name, q, bytes);
   return 0;
 }
 
@@ -593,6 +604,9 @@ int mmu_seqattn_fwd(const void* QKV, int64_t ld_qkv, void* O, int64_t ld_o, floa
   if (!QKV || !O || !LSE2) return fail("mmu_seqattn_fwd: null pointer");
   if (seqattn_check("mmu_seqattn_fwd", ld_qkv, S, N, heads, head_dim)) return 1;
   if (ld_o < heads * head_dim || ld_o % 4) return fail("mmu_seqattn_fwd: bad ld_o");
+  if (seqattn_aligned("mmu_seqattn_fwd", "QKV", QKV, 16) || seqattn_aligned("mmu_seqattn_fwd", "O", O, 8) ||
+      seqattn_aligned("mmu_seqattn_fwd", "LSE2", LSE2, 4))
+    return 1;
   SeqAttnParams p{};
   p.qkv = (const bf16*)QKV; p.ld_qkv = ld_qkv;
   p.out = (bf16*)O; p.ld_out = ld_o;
@@ -609,6 +623,19 @@ int mmu_seqattn_bwd(const void* QKV, int64_t ld_qkv, const void* O, int64_t ld_o
   if (!QKV || !O || !dO || !LSE2 || !delta || !dQKV) return fail("mmu_seqattn_bwd: null pointer");
   if (seqattn_check("mmu_seqattn_bwd", ld_qkv, S, N, heads, head_dim)) return 1;
   if (ld_dqkv < 3 * heads * head_dim || ld_dqkv % 4 || ld_o % 4 || ld_do % 8) return fail("mmu_seqattn_bwd: bad ld");
+  if (ld_o < heads * head_dim)
+    return fail("mmu_seqattn_bwd: ld_o = %ld is smaller than heads*head_dim = %ld", ld_o, heads * head_dim);
+  if (ld_do < heads * head_dim)
+    return fail("mmu_seqattn_bwd: ld_do = %ld is smaller than heads*head_dim = %ld", ld_do, heads * head_dim);
+  const char* const who = "mmu_seqattn_bwd";
+  if (seqattn_aligned(who, "QKV", QKV, 16) || seqattn_aligned(who, "dO", dO, 16) || seqattn_aligned(who, "O", O, 8) ||
+      seqattn_aligned(who, "dQKV", dQKV, 8) || seqattn_aligned(who, "LSE2", LSE2, 4) ||
+      seqattn_aligned(who, "delta", delta, 4))
+    return 1;
+  // the delta kernel's grid: one block per 4 (row, head) items, in the grid's x dimension
+  if ((S * N * heads + 3) / 4 > (int64_t)INT32_MAX)
+    return fail("mmu_seqattn_bwd: S*N*heads = %ld needs more than %ld delta blocks (the grid's x limit)",
+                S * N * heads, (int64_t)INT32_MAX);
   SeqAttnParams p{};
   p.qkv = (const bf16*)QKV; p.ld_qkv = ld_qkv;
   p.o = (const bf16*)O; p.ld_o = ld_o;

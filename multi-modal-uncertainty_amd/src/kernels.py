@@ -603,24 +603,76 @@ def layernorm_bwd_res(dY, X, mean, rstd, w, dRes, dX, part_dw=None, part_db=None
            _ptr(part_dw), _ptr(part_db), _ptr(part_dbias), rows, H, LN_ROWS_PER_PART, _stream(X))
 
 
+def _seqattn_refuse(who, qkv, S, N_, heads, rows=(), vecs=()):
+    """Names what is wrong with the arguments of a seqattn wrapper (the slow path of the checks
+    below: shapes, dtypes and strides only).  qkv: [>= S*N, 3E] bf16 rows; rows: (name, tensor, width
+    in units of E) bf16 row sets of >= S*N rows (row stride free, inner stride 1); vecs: (name,
+    tensor) contiguous f32 vectors of >= S*N*heads elements."""
+    S, N_, heads = int(S), int(N_), int(heads)
+    if S <= 0 or N_ <= 0 or heads <= 0:
+        raise N.NativeError(f"{who}: S = {S}, N = {N_}, heads = {heads} must be positive")
+    if qkv.dim() != 2 or qkv.shape[1] == 0 or qkv.shape[1] % (3 * heads):
+        raise N.NativeError(f"{who}: qkv must be 2-D [S*N, 3E] with 3E divisible by 3*heads = {3 * heads}, got "
+                            f"{tuple(qkv.shape)}")
+    E = qkv.shape[1] // 3
+    for name, t, w in (("qkv", qkv, 3),) + tuple(rows):
+        _want(t, torch.bfloat16, f"{who} {name}")
+        if t.dim() != 2 or t.shape[1] != w * E:
+            raise N.NativeError(f"{who}: {name} must be 2-D of width {w * E}, got {tuple(t.shape)}")
+        if t.stride(1) != 1:
+            raise N.NativeError(f"{who}: the inner stride of {name} must be 1, got {t.stride(1)}")
+        if t.shape[0] < S * N_:
+            raise N.NativeError(f"{who}: {name} has {t.shape[0]} rows, S*N = {S * N_} are needed")
+    for name, t in vecs:
+        _want(t, torch.float32, f"{who} {name}")
+        if t.numel() < S * N_ * heads:
+            raise ValueError(f"{who}: {name} too small")
+        if not t.is_contiguous():
+            raise N.NativeError(f"{who}: {name} must be contiguous, got strides {tuple(t.stride())}")
+    raise N.NativeError(f"{who}: arguments refused")  # not reached: _seq_ld / _seq_vec_ok test the same things
+
+
+def _seq_ld(t, width, rows):
+    """the row stride of a bf16 row set [>= rows, width] with inner stride 1, or -1 (the wrappers run
+    once per layer and step: one pass, no message built unless something is wrong)"""
+    sh, st = t.shape, t.stride()
+    if t.dtype is torch.bfloat16 and len(sh) == 2 and sh[1] == width and sh[0] >= rows and st[1] == 1:
+        return st[0]
+    return -1
+
+
+def _seq_vec_ok(t, n):
+    return t.dtype is torch.float32 and t.numel() >= n and t.is_contiguous()
+
+
 def seqattn_fwd(qkv, O, lse2, S, N_, heads):
     """FLAVA attention over the sequence (= batch) axis; see mmu_seqattn_fwd."""
+    W = qkv.shape[1] if qkv.dim() == 2 else 0
+    ok = S > 0 and N_ > 0 and heads > 0 and W > 0 and W % (3 * heads) == 0
+    E, R = W // 3, S * N_
+    if ok:
+        ld_qkv, ld_o = _seq_ld(qkv, W, R), _seq_ld(O, E, R)
+        ok = ld_qkv >= 0 and ld_o >= 0 and _seq_vec_ok(lse2, R * heads)
+    if not ok:
+        _seqattn_refuse("seqattn_fwd", qkv, S, N_, heads, rows=(("O", O, 1),), vecs=(("lse2", lse2),))
     _dev_check(qkv, O, lse2)
-    _want(qkv, torch.bfloat16, "seqattn qkv")
-    D = qkv.shape[1] // (3 * heads)
-    if lse2.numel() < S * N_ * heads:
-        raise ValueError("seqattn_fwd: lse2 too small")
-    N.call("mmu_seqattn_fwd", _ptr(qkv), qkv.stride(0), _ptr(O), O.stride(0), _ptr(lse2), S, N_, heads, D,
-           _stream(qkv))
+    N.call("mmu_seqattn_fwd", _ptr(qkv), ld_qkv, _ptr(O), ld_o, _ptr(lse2), S, N_, heads, E // heads, _stream(qkv))
 
 
 def seqattn_bwd(qkv, O, dO, lse2, delta, dqkv, S, N_, heads):
+    W = qkv.shape[1] if qkv.dim() == 2 else 0
+    ok = S > 0 and N_ > 0 and heads > 0 and W > 0 and W % (3 * heads) == 0
+    E, R = W // 3, S * N_
+    if ok:
+        ld_qkv, ld_o, ld_do, ld_dqkv = _seq_ld(qkv, W, R), _seq_ld(O, E, R), _seq_ld(dO, E, R), _seq_ld(dqkv, W, R)
+        ok = ld_qkv >= 0 and ld_o >= 0 and ld_do >= 0 and ld_dqkv >= 0 and _seq_vec_ok(lse2, R * heads) \
+            and _seq_vec_ok(delta, R * heads)
+    if not ok:
+        _seqattn_refuse("seqattn_bwd", qkv, S, N_, heads, rows=(("O", O, 1), ("dO", dO, 1), ("dqkv", dqkv, 3)),
+                        vecs=(("lse2", lse2), ("delta", delta)))
     _dev_check(qkv, O, dO, lse2, delta, dqkv)
-    D = qkv.shape[1] // (3 * heads)
-    if delta.numel() < S * N_ * heads:
-        raise ValueError("seqattn_bwd: delta too small")
-    N.call("mmu_seqattn_bwd", _ptr(qkv), qkv.stride(0), _ptr(O), O.stride(0), _ptr(dO), dO.stride(0), _ptr(lse2),
-           _ptr(delta), _ptr(dqkv), dqkv.stride(0), S, N_, heads, D, _stream(qkv))
+    N.call("mmu_seqattn_bwd", _ptr(qkv), ld_qkv, _ptr(O), ld_o, _ptr(dO), ld_do, _ptr(lse2), _ptr(delta), _ptr(dqkv),
+           ld_dqkv, S, N_, heads, E // heads, _stream(qkv))
 
 
 EMBED_WIDTHS = (768, 1024)  # the widths embed.hip instantiates (bert-base, bert-large)

@@ -1,7 +1,7 @@
 """Guarded device buffers for the kernel edge sweeps (test_attention_edges_gpu.py,
 test_layernorm_edges_gpu.py, test_embed_edges_gpu.py, test_batchnorm_edges_gpu.py,
 test_bertadam_edges_gpu.py, test_gemm_edges_gpu.py, test_conv_edges_gpu.py, test_stem_edges_gpu.py,
-test_pool_edges_gpu.py): every tensor a kernel sees is a view of a larger allocation.  Input guards hold NaN, so a read through them poisons the result; outputs are
+test_pool_edges_gpu.py, test_seqattn_edges_gpu.py): every tensor a kernel sees is a view of a larger allocation.  Input guards hold NaN, so a read through them poisons the result; outputs are
 pre-filled with a canary, and afterwards everything outside the view must be bit-identical to it.
   out_buf / check_written: NaN-filled contiguous outputs and their check after a launch;
   probe_keep: the keep bits of the GEMM's BIAS_DROP_RES epilogue, read from the epilogue itself.

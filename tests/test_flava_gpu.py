@@ -61,6 +61,38 @@ def test_seqattn_fwd_bwd(dev, S, N, heads):
         close(dqkv[:, i * E:(i + 1) * E], q32.grad[:, i * E:(i + 1) * E], frac=2e-2)
 
 
+def test_seqattn_fwd_bwd_padded_views(dev):
+    """the same comparison through column slices of wider allocations: the wrappers pass stride(0) as
+    the leading dimensions (ld_qkv = 3E + 8, ld_o = E + 4, ld_do = E + 8, ld_dqkv = 3E + 4), and the
+    padding columns stay as they were"""
+    k = K()
+    S, N, heads, E = 70, 2, 3, 768
+
+    def padded(rows, width, ld, data=None):
+        full = torch.full((rows, ld), float("nan"), dtype=torch.bfloat16, device=dev)
+        if data is not None:
+            full[:, :width] = data
+        return full, full[:, :width]
+
+    _, qkv = padded(S * N, 3 * E, 3 * E + 8, rnd(S * N, 3 * E, dev=dev, seed=1))
+    _, dO = padded(S * N, E, E + 8, rnd(S * N, E, dev=dev, seed=2))
+    Of, O = padded(S * N, E, E + 4)
+    gf, dqkv = padded(S * N, 3 * E, 3 * E + 4)
+    assert (qkv.stride(0), O.stride(0), dO.stride(0), dqkv.stride(0)) == (3 * E + 8, E + 4, E + 8, 3 * E + 4)
+    lse2 = torch.empty(N * heads, S, device=dev)
+    delta = torch.empty(N * heads, S, device=dev)
+    k.seqattn_fwd(qkv, O, lse2, S, N, heads)
+    q32 = qkv.float().requires_grad_(True)
+    ref = seq_ref(q32, S, N, heads)
+    close(O, ref)
+    ref.backward(dO.float())
+    k.seqattn_bwd(qkv, O, dO, lse2, delta, dqkv, S, N, heads)
+    assert torch.isfinite(dqkv.float()).all(), "dQKV not fully written"
+    for i in range(3):
+        close(dqkv[:, i * E:(i + 1) * E], q32.grad[:, i * E:(i + 1) * E], frac=2e-2)
+    assert torch.isnan(Of[:, E:].float()).all() and torch.isnan(gf[:, 3 * E:].float()).all(), "padding written"
+
+
 def test_gemm_bias_dropout_quickgelu(dev):
     k = K()
     M, N, Kd = 300, 384, 256
