@@ -64,7 +64,8 @@ int mmu_set_seed_offset(const uint64_t* dev_counter);
  *     on (16-B aligned);
  *   mmu_uncertainty_decompose launches the same kernel in both modes: it has no atomics, its
  *     sums fold in a fixed lane and wave order, so its result depends on the inputs and the
- *     shape alone and is bitwise repeatable with the mode on or off; mmu_robustness_summary likewise. */
+ *     shape alone and is bitwise repeatable with the mode on or off; mmu_robustness_summary,
+ *     mmu_uncertainty_decompose_scaled and mmu_temperature_nll likewise. */
 int mmu_set_deterministic(int on); /* -> the previous value */
 int mmu_get_deterministic(void);
 
@@ -600,6 +601,38 @@ enum {
 int mmu_uncertainty_decompose(const float* logits, int64_t ss, int64_t sk, int64_t st, const int64_t* y,
                               int64_t S, int64_t K, int64_t T, int64_t C, float* stats, float* p_bar,
                               float* member_nll, mmu_stream_t stream);
+
+/* Temperature scaling of the ensemble (new symbols, ABI stays 4).  Inverse temperature beta = 1 / tau,
+ * one per member: beta in R^K, beta_k >= 0 and finite.  For sample s with rows z_kt in R^C and label y:
+ *   p_kt(beta) = softmax(beta_k z_kt)     p_k = mean_t p_kt     p(beta) = mean_k p_k
+ *   nll_s(beta) = -ln max(p(beta)_y, 1e-12)                      (the floor of mmu_uncertainty)
+ * A label outside [0, C) gives p_y = 0, so nll = -ln 1e-12 (class indices are compared with y, never
+ * indexed by it, as in mmu_robustness_summary).  "Shared" temperature: all beta_k equal; "per-member":
+ * beta a free K-vector; beta = 1 is the unscaled pipeline.
+ *
+ * mmu_uncertainty_decompose_scaled: the table of mmu_uncertainty_decompose with z_kt replaced by
+ * beta_k z_kt (all nine columns, p_bar and member_nll); inv_temp device f32 [K], or NULL = all ones.
+ * With inv_temp NULL or all ones its outputs are bitwise those of mmu_uncertainty_decompose on the
+ * same input (NULL launches the very same kernel; 1 * z is z).  Refusals as mmu_uncertainty_decompose.
+ *
+ * mmu_temperature_nll: the NLL of J candidate vectors in one read of the logits, addressed exactly as
+ * in mmu_uncertainty_decompose (element strides, class axis contiguous: [K, T, S, C] in place and
+ * [S, K, T, C]).  inv_temp device f32 [J, K] (row j = candidate j); 1 <= C <= 1024, 1 <= J <= 64.
+ *   nll f32 [S, J]:      nll[s, j] = nll_s(inv_temp[j, :])
+ *   nll_sum f64 [J]:     sum_s nll[s, j], accumulated in f64 in one fixed order (a second small launch
+ *                        on the same stream), or NULL
+ * A row is loaded once and its max taken once (max(beta z) = beta max z for beta >= 0); expf / logf, no
+ * atomics, every sum in one fixed order: bitwise repeatable in both determinism modes, and a
+ * candidate's figures do not depend on the other candidates of the launch.  Refused before any
+ * launch: null logits / y / inv_temp / nll, non-positive S / K / T / C / J, C > 1024, J > 64, and the
+ * stride checks of mmu_uncertainty_decompose.  The CONTENTS of inv_temp (finite, >= 0) are device
+ * memory and the caller's contract. */
+int mmu_uncertainty_decompose_scaled(const float* logits, int64_t ss, int64_t sk, int64_t st, const int64_t* y,
+                                     int64_t S, int64_t K, int64_t T, int64_t C, float* stats, float* p_bar,
+                                     float* member_nll, const float* inv_temp, mmu_stream_t stream);
+int mmu_temperature_nll(const float* logits, int64_t ss, int64_t sk, int64_t st, const int64_t* y, int64_t S,
+                        int64_t K, int64_t T, int64_t C, const float* inv_temp, int64_t J, float* nll,
+                        double* nll_sum, mmu_stream_t stream);
 
 /* Modality-reliance summary of the robustness stack, per sample (the analysis the reference does in
  * notebooks/food101_robustness.py + notebooks/utils.py on the saved [S, 3 + 2n, C] predictions:

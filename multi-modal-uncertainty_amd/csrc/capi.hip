@@ -1115,21 +1115,10 @@ int mmu_ece_bins(const float* conf, const float* correct, int64_t S, int64_t n_b
   return check_launch("mmu_ece_bins");
 }
 
-int mmu_uncertainty_decompose(const float* logits, int64_t ss, int64_t sk, int64_t st, const int64_t* y, int64_t S,
-                              int64_t K, int64_t T, int64_t C, float* stats, float* p_bar, float* member_nll,
-                              mmu_stream_t stream) {
-  const char* who = "mmu_uncertainty_decompose";
-  if (!logits) return fail("%s: logits is null", who);
-  if (!y) return fail("%s: y is null", who);
-  if (!stats) return fail("%s: stats is null", who);
-  if (!p_bar) return fail("%s: p_bar is null", who);
-  if (S <= 0) return fail("%s: S = %lld must be positive", who, (long long)S);
-  if (K <= 0) return fail("%s: K = %lld must be positive", who, (long long)K);
-  if (T <= 0) return fail("%s: T = %lld must be positive", who, (long long)T);
-  if (C <= 0) return fail("%s: C = %lld must be positive", who, (long long)C);
-  if (C > 1024) return fail("%s: C = %lld exceeds 1024 classes", who, (long long)C);
-  if (S > 0x7fffffffLL) return fail("%s: S = %lld exceeds the grid limit 2147483647", who, (long long)S);
-  // the axes that step (extent > 1), by ascending stride: each must clear the span of the one below it
+// element strides of an [S, K, T, C] logit stack with a contiguous class axis: the axes that step
+// (extent > 1), by ascending stride, must each clear the span of the one below it
+static int check_skt_strides(const char* who, int64_t ss, int64_t sk, int64_t st, int64_t S, int64_t K, int64_t T,
+                             int64_t C) {
   struct Axis { const char* name; int64_t stride, extent; } ax[3] = {{"ss", ss, S}, {"sk", sk, K}, {"st", st, T}};
   for (int i = 1; i < 3; ++i)
     for (int j = i; j > 0 && ax[j].stride < ax[j - 1].stride; --j) std::swap(ax[j], ax[j - 1]);
@@ -1144,7 +1133,63 @@ int mmu_uncertainty_decompose(const float* logits, int64_t ss, int64_t sk, int64
     span = a.stride * a.extent;
     below = a.name;
   }
-  uncertainty_decompose_launch(logits, ss, sk, st, y, S, K, T, C, stats, p_bar, member_nll, (hipStream_t)stream);
+  return 0;
+}
+
+// the refusals mmu_uncertainty_decompose and mmu_uncertainty_decompose_scaled share
+static int decompose_check(const char* who, const float* logits, int64_t ss, int64_t sk, int64_t st, const int64_t* y,
+                           int64_t S, int64_t K, int64_t T, int64_t C, float* stats, float* p_bar) {
+  if (!logits) return fail("%s: logits is null", who);
+  if (!y) return fail("%s: y is null", who);
+  if (!stats) return fail("%s: stats is null", who);
+  if (!p_bar) return fail("%s: p_bar is null", who);
+  if (S <= 0) return fail("%s: S = %lld must be positive", who, (long long)S);
+  if (K <= 0) return fail("%s: K = %lld must be positive", who, (long long)K);
+  if (T <= 0) return fail("%s: T = %lld must be positive", who, (long long)T);
+  if (C <= 0) return fail("%s: C = %lld must be positive", who, (long long)C);
+  if (C > 1024) return fail("%s: C = %lld exceeds 1024 classes", who, (long long)C);
+  if (S > 0x7fffffffLL) return fail("%s: S = %lld exceeds the grid limit 2147483647", who, (long long)S);
+  return check_skt_strides(who, ss, sk, st, S, K, T, C);
+}
+
+int mmu_uncertainty_decompose(const float* logits, int64_t ss, int64_t sk, int64_t st, const int64_t* y, int64_t S,
+                              int64_t K, int64_t T, int64_t C, float* stats, float* p_bar, float* member_nll,
+                              mmu_stream_t stream) {
+  const char* who = "mmu_uncertainty_decompose";
+  if (decompose_check(who, logits, ss, sk, st, y, S, K, T, C, stats, p_bar)) return 1;
+  uncertainty_decompose_launch(logits, ss, sk, st, y, S, K, T, C, stats, p_bar, member_nll, nullptr,
+                               (hipStream_t)stream);
+  return check_launch(who);
+}
+
+int mmu_uncertainty_decompose_scaled(const float* logits, int64_t ss, int64_t sk, int64_t st, const int64_t* y,
+                                     int64_t S, int64_t K, int64_t T, int64_t C, float* stats, float* p_bar,
+                                     float* member_nll, const float* inv_temp, mmu_stream_t stream) {
+  const char* who = "mmu_uncertainty_decompose_scaled";
+  if (decompose_check(who, logits, ss, sk, st, y, S, K, T, C, stats, p_bar)) return 1;
+  uncertainty_decompose_launch(logits, ss, sk, st, y, S, K, T, C, stats, p_bar, member_nll, inv_temp,
+                               (hipStream_t)stream);
+  return check_launch(who);
+}
+
+int mmu_temperature_nll(const float* logits, int64_t ss, int64_t sk, int64_t st, const int64_t* y, int64_t S,
+                        int64_t K, int64_t T, int64_t C, const float* inv_temp, int64_t J, float* nll,
+                        double* nll_sum, mmu_stream_t stream) {
+  const char* who = "mmu_temperature_nll";
+  if (!logits) return fail("%s: logits is null", who);
+  if (!y) return fail("%s: y is null", who);
+  if (!inv_temp) return fail("%s: inv_temp is null", who);
+  if (!nll) return fail("%s: nll is null", who);
+  if (S <= 0) return fail("%s: S = %lld must be positive", who, (long long)S);
+  if (K <= 0) return fail("%s: K = %lld must be positive", who, (long long)K);
+  if (T <= 0) return fail("%s: T = %lld must be positive", who, (long long)T);
+  if (C <= 0) return fail("%s: C = %lld must be positive", who, (long long)C);
+  if (J <= 0) return fail("%s: J = %lld must be positive", who, (long long)J);
+  if (C > 1024) return fail("%s: C = %lld exceeds 1024 classes", who, (long long)C);
+  if (J > 64) return fail("%s: J = %lld exceeds 64 candidates", who, (long long)J);
+  if (S > 0x7fffffffLL) return fail("%s: S = %lld exceeds the grid limit 2147483647", who, (long long)S);
+  if (check_skt_strides(who, ss, sk, st, S, K, T, C)) return 1;
+  temperature_nll_launch(logits, ss, sk, st, y, S, K, T, C, inv_temp, J, nll, nll_sum, (hipStream_t)stream);
   return check_launch(who);
 }
 

@@ -249,7 +249,10 @@ void uncertainty_launch(const float* logits, const int64_t* y, int64_t S, int64_
 void ece_bins_launch(const float* conf, const float* correct, int64_t S, int64_t n_bins, float* out, hipStream_t s);
 void uncertainty_decompose_launch(const float* logits, int64_t ss, int64_t sk, int64_t st, const int64_t* y, int64_t S,
                                   int64_t K, int64_t T, int64_t C, float* stats, float* p_bar, float* member_nll,
-                                  hipStream_t s);
+                                  const float* inv_temp /* [K], or NULL: unscaled */, hipStream_t s);
+void temperature_nll_launch(const float* logits, int64_t ss, int64_t sk, int64_t st, const int64_t* y, int64_t S,
+                            int64_t K, int64_t T, int64_t C, const float* inv_temp, int64_t J, float* nll,
+                            double* nll_sum, hipStream_t s);
 void robustness_summary_launch(const float* logits, int64_t ss, int64_t sv, int64_t sk, const int64_t* y, int64_t S,
                                int64_t V, int64_t K, int64_t C, float* stats, float* per_variant, hipStream_t s);
 

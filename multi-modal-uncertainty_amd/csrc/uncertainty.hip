@@ -142,10 +142,13 @@ static __device__ __forceinline__ void wave_argmax(float& best, int& arg) {
   }
 }
 
-template <int NJ>
+// SCALED (mmu_uncertainty_decompose_scaled): member k's logits are multiplied by inv_temp[k] as they
+// are loaded, and everything below sees beta_k z_kt; the unscaled instantiation never reads inv_temp.
+template <int NJ, bool SCALED>
 __global__ __launch_bounds__(UD_THREADS) void uncertainty_decompose_kernel(
     const float* __restrict__ logits, int64_t ss, int64_t sk, int64_t st, const int64_t* __restrict__ y, int64_t K,
-    int64_t T, int64_t C, float* __restrict__ stats, float* __restrict__ p_bar, float* __restrict__ member_nll) {
+    int64_t T, int64_t C, float* __restrict__ stats, float* __restrict__ p_bar, float* __restrict__ member_nll,
+    const float* __restrict__ inv_temp) {
   constexpr int NI = NJ * 64 > UD_THREADS ? NJ * 64 / UD_THREADS : 1;  // classes per thread in the fold
   __shared__ float part[UD_WAVES][NJ * 64];
   __shared__ double red_d[UD_WAVES][4];
@@ -168,6 +171,8 @@ __global__ __launch_bounds__(UD_THREADS) void uncertainty_decompose_kernel(
     float acc[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) acc[j] = 0.f;
+    float beta = 1.f;
+    if constexpr (SCALED) beta = inv_temp[k];
     for (int64_t t = wave; t < T; t += UD_WAVES) {
       const float* z = logits + s * ss + k * sk + t * st;
       float v[NJ];
@@ -176,7 +181,8 @@ __global__ __launch_bounds__(UD_THREADS) void uncertainty_decompose_kernel(
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
         const int c = lane + 64 * j;
-        v[j] = c < C ? z[c] : -__builtin_huge_valf();
+        if constexpr (SCALED) v[j] = c < C ? beta * z[c] : -__builtin_huge_valf();
+        else v[j] = c < C ? z[c] : -__builtin_huge_valf();
         if (v[j] > best) { best = v[j]; arg = c; }
       }
       wave_argmax(best, arg);
@@ -293,10 +299,16 @@ __global__ __launch_bounds__(UD_THREADS) void uncertainty_decompose_kernel(
 
 void uncertainty_decompose_launch(const float* logits, int64_t ss, int64_t sk, int64_t st, const int64_t* y, int64_t S,
                                   int64_t K, int64_t T, int64_t C, float* stats, float* p_bar, float* member_nll,
-                                  hipStream_t s) {
-#define MMU_UD_LAUNCH(NJ)                                                                                          \
-  hipLaunchKernelGGL(uncertainty_decompose_kernel<NJ>, dim3((unsigned)S), dim3(UD_THREADS), 0, s, logits, ss, sk, \
-                     st, y, K, T, C, stats, p_bar, member_nll)
+                                  const float* inv_temp, hipStream_t s) {
+#define MMU_UD_LAUNCH(NJ)                                                                                      \
+  do {                                                                                                         \
+    if (inv_temp)                                                                                              \
+      hipLaunchKernelGGL((uncertainty_decompose_kernel<NJ, true>), dim3((unsigned)S), dim3(UD_THREADS), 0, s, \
+                         logits, ss, sk, st, y, K, T, C, stats, p_bar, member_nll, inv_temp);                  \
+    else                                                                                                       \
+      hipLaunchKernelGGL((uncertainty_decompose_kernel<NJ, false>), dim3((unsigned)S), dim3(UD_THREADS), 0, s, \
+                         logits, ss, sk, st, y, K, T, C, stats, p_bar, member_nll, inv_temp);                  \
+  } while (0)
   if (C <= 64) MMU_UD_LAUNCH(1);
   else if (C <= 128) MMU_UD_LAUNCH(2);
   else if (C <= 256) MMU_UD_LAUNCH(4);

@@ -14,6 +14,14 @@ Brier score, vote disagreement, per-member NLL, ensemble gain and error-detectio
 src/uncertainty.py UncertaintyMeter(decompose=True)) and "variants" (the same, with nll / ece / acc,
 per requested variant; every variant but full is a logits call of its own on the same batch and
 also writes <save_path>/uncertainty_<phase>_<variant>_logits.npy).
+With --calibrate {shared,per_member} [--calibrate_phase val] the ensemble first runs over the
+calibration phase and its temperature(s) are fitted on the device (src/calibration.py); --temperature
+FILE applies a saved fit instead.  Either way --phase then runs as above, a second decomposition meter
+reads the same logits under the fitted temperatures, the metrics gain "calibrated" (and, with
+"variants", "variants_calibrated": every variant under the full forward's temperature) and
+  <save_path>/uncertainty_<phase>_calibration.json {mode, tau, nll_before, nll_after, passes, rounds,
+      at_bound, fit_phase, eval_phase, same_split, before, after}
+is written (before / after: nll, ece, brier, acc, total, mi); the file is itself a valid --temperature.
 Without --mmbt: the reference's FashionMNIST MIMO robustness pass (eval_robustness.py:42-121,
 BASELINE config 1's model family): each of the 4 quarter-crop views zeroed in turn (the
 weight-sharing model sees the other 3), predictions [4, S, heads, 10] and labels written as
@@ -57,6 +65,11 @@ FLAGS = [
     ("--decompose", dict(action="store_true")),
     ("--variants", dict(nargs="+", default=["full"],
                         choices=["full", "img_only", "txt_only", "control_image", "control_text"])),
+    # MMBT uncertainty mode: temperature scaling (src/calibration.py)
+    ("--calibrate", dict(type=str, default=None, choices=["shared", "per_member"],
+                         help="fit the ensemble's temperature(s) on --calibrate_phase and report --phase under them")),
+    ("--calibrate_phase", dict(type=str, default="val")),
+    ("--temperature", dict(type=str, default=None, help="apply a saved fit (a calibration JSON) instead of fitting")),
 ]
 
 # --variants name -> EnsembleMMBT.logits(variant=...)
@@ -76,6 +89,35 @@ def mmbt_model_args(args, n_classes, vocab):
                      bert_model=args.bert_model, hidden_sz=args.hidden_sz)
 
 
+# what uncertainty_<phase>_calibration.json compares before and after temperature scaling
+CALIBRATION_KEYS = ("nll", "ece", "brier", "acc", "total", "mi")
+
+
+def check_calibration_flags(args):
+    if args.calibrate and args.temperature:
+        raise ValueError("--calibrate fits a temperature and --temperature applies a saved one: give one of them")
+
+
+def fit_temperature_on(args, ens, loader, dev):
+    """--calibrate: the ensemble over ``loader``, its logits kept on the device, and the fit.  The torch
+    generator states are put back afterwards, so the evaluation pass that follows draws the dropout
+    seeds (and a shuffling loader's order) of a run without the flag."""
+    from src.calibration import TemperatureScaler
+    cpu_state, dev_state = torch.get_rng_state(), torch.cuda.get_rng_state(dev)
+    scaler = TemperatureScaler(args.calibrate)
+    try:
+        with torch.no_grad():
+            for x, y in loader:
+                txt, segment, mask, img = (t.to(dev) for t in x)
+                scaler.add(ens.logits(txt, segment, mask, img, mc_samples=args.mc_samples), y.to(dev))
+        scaler.fit()
+    finally:
+        scaler.clear()
+        torch.set_rng_state(cpu_state)
+        torch.cuda.set_rng_state(dev_state, dev)
+    return scaler
+
+
 def run_mmbt(args):
     from src import gin
     from src.mmbt import MultimodalBertClf
@@ -83,6 +125,7 @@ def run_mmbt(args):
     from src.uncertainty import EnsembleMMBT, UncertaintyMeter
     from src.utils import set_seed
     from eval_mmbt_robustness import load_data
+    check_calibration_flags(args)
     set_seed(args.seed)
     args.drop_img_percent = 0.0
     data, n_classes, vocab = load_data(args)
@@ -105,11 +148,39 @@ def run_mmbt(args):
     extra = [v for v in dict.fromkeys(args.variants) if v != "full"]
     meter = UncertaintyMeter(args.n_bins, decompose=decompose)
     vmeters = {v: UncertaintyMeter(args.n_bins, decompose=True) for v in extra}
+    # --calibrate / --temperature: a second decompose meter reads the same logits under the fitted
+    # temperatures (the ensemble is not run again), and one more per variant, under the full forward's
+    scaler, fit_phase = None, None
+    if args.temperature:
+        from src.calibration import TemperatureScaler
+        scaler = TemperatureScaler.load(args.temperature)
+        fit_phase = scaler.extra.get("fit_phase")      # a calibration JSON names it, a bare save() file does not
+    elif args.calibrate:
+        scaler, fit_phase = fit_temperature_on(args, ens, data[args.calibrate_phase], dev), args.calibrate_phase
+    if scaler is not None:
+        if len(scaler.result["tau"]) != len(members):
+            raise ValueError(f"the temperature fit holds {len(scaler.result['tau'])} members, the ensemble "
+                             f"{len(members)}")
+        same_split = None if fit_phase is None else fit_phase == args.phase
+        if fit_phase is None:
+            print(f"NOTE: {args.temperature} does not say which split it was fitted on: whether that was "
+                  f"{args.phase} is not known")
+        if same_split:
+            print(f"WARNING: the temperature was fitted on the split it is evaluated on ({args.phase}): the "
+                  "calibrated figures are optimistic")
+        inv_temp = scaler.inv_temp(dev)
+        before = meter if decompose else UncertaintyMeter(args.n_bins, decompose=True)
+        after = UncertaintyMeter(args.n_bins, decompose=True, inv_temp=inv_temp)
+        vafter = {v: UncertaintyMeter(args.n_bins, decompose=True, inv_temp=inv_temp) for v in extra}
     all_logits, labels, vlogits = [], [], {v: [] for v in extra}
     with torch.no_grad():
         for x, y in data[args.phase]:
             txt, segment, mask, img = (t.to(dev) for t in x)
             lo = ens.logits(txt, segment, mask, img, mc_samples=args.mc_samples)   # [K, T, B, C]
+            if scaler is not None:
+                if before is not meter:
+                    before.update(lo, y.to(dev))
+                after.update(lo, y.to(dev))
             if decompose:
                 meter.update(lo, y.to(dev))
             else:
@@ -120,6 +191,8 @@ def run_mmbt(args):
             for v in extra:
                 lv = ens.logits(txt, segment, mask, img, mc_samples=args.mc_samples, variant=VARIANTS[v])
                 vmeters[v].update(lv, y.to(dev))
+                if scaler is not None:
+                    vafter[v].update(lv, y.to(dev))
                 vlogits[v].append(lv.permute(2, 0, 1, 3).cpu())
     full = meter.result()
     res = dict({k: full[k] for k in ("nll", "ece", "acc", "n")}, K=len(members), T=args.mc_samples)
@@ -127,6 +200,17 @@ def run_mmbt(args):
         res["decomposition"] = {k: v for k, v in full.items() if k not in ("nll", "ece", "acc", "n")}
         res["variants"] = {v: full if v == "full" else vmeters[v].result() for v in dict.fromkeys(args.variants)}
     os.makedirs(args.save_path, exist_ok=True)
+    if scaler is not None:
+        cal_full = after.result()
+        cal = dict(scaler.result, fit_phase=fit_phase, eval_phase=args.phase, same_split=same_split,
+                   before={k: before.result()[k] for k in CALIBRATION_KEYS},
+                   after={k: cal_full[k] for k in CALIBRATION_KEYS})
+        res["calibrated"] = cal["after"]
+        if decompose:
+            res["variants_calibrated"] = {v: cal_full if v == "full" else vafter[v].result()
+                                          for v in dict.fromkeys(args.variants)}
+        with open(os.path.join(args.save_path, f"uncertainty_{args.phase}_calibration.json"), "w") as f:
+            json.dump(cal, f, indent=1, allow_nan=False)
     np.save(os.path.join(args.save_path, f"uncertainty_{args.phase}_logits.npy"), torch.cat(all_logits).numpy())
     for v in extra:   # (the full forward's logits are the file above)
         np.save(os.path.join(args.save_path, f"uncertainty_{args.phase}_{v}_logits.npy"),

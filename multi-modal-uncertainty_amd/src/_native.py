@@ -115,6 +115,10 @@ SIGNATURES = {
     "mmu_ece_bins": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "mmu_uncertainty_decompose": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp,
                                           c_vp, c_vp]),
+    "mmu_uncertainty_decompose_scaled": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp,
+                                                 c_vp, c_vp, c_vp, c_vp]),
+    "mmu_temperature_nll": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp,
+                                    c_vp, c_vp]),
     "mmu_robustness_summary": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp,
                                        c_vp]),
     "mmu_gemm_plan": (c_i32, [c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64,

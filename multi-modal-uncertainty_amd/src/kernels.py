@@ -5,6 +5,7 @@ device and raises if a tensor is not on a HIP device or has the wrong
 dtype/layout -- there is no CPU fallback ("no fallback").
 """
 import ctypes
+import weakref
 
 import torch
 
@@ -1224,10 +1225,32 @@ UNC_COLUMNS = ("total", "aleatoric", "mi_members", "mi_passes", "brier", "nll", 
 UNC_NSTAT = len(UNC_COLUMNS)
 
 
-def uncertainty_decompose(logits, y, stats, p_bar, member_nll=None):
+_inv_temp_seen = None   # (weakref to the last table whose contents passed, its version counter)
+
+
+def _inv_temp_check(who, inv_temp, shape, what):
+    """an inverse-temperature table: contiguous f32 of the given shape, every entry finite and >= 0
+    (the library cannot look into device memory).  Reading the verdict back synchronises the device, so
+    it is done once per table: the same tensor, not written in place since, is not read again -- a meter
+    that passes one [K] tensor on every update pays for the first."""
+    global _inv_temp_seen
+    _want(inv_temp, torch.float32, "inv_temp")
+    if tuple(inv_temp.shape) != shape or not inv_temp.is_contiguous():
+        raise N.NativeError(f"{who}: inv_temp must be contiguous f32 {what} = {list(shape)}, got "
+                            f"{tuple(inv_temp.shape)}")
+    if _inv_temp_seen is not None and _inv_temp_seen[0]() is inv_temp and _inv_temp_seen[1] == inv_temp._version:
+        return
+    if not bool((torch.isfinite(inv_temp) & (inv_temp >= 0)).all()):
+        raise N.NativeError(f"{who}: every inverse temperature must be finite and >= 0")
+    _inv_temp_seen = (weakref.ref(inv_temp), inv_temp._version)
+
+
+def uncertainty_decompose(logits, y, stats, p_bar, member_nll=None, inv_temp=None):
     """logits f32 [S, K, T, C], any strides with a contiguous class axis (``lo.permute(2, 0, 1, 3)`` of the
     [K, T, B, C] ensemble logits is read in place), y int64 [S] -> stats f32 [S, UNC_NSTAT] (columns
-    UNC_COLUMNS), p_bar f32 [S, C], member_nll f32 [S, K] or None (mmu_uncertainty_decompose)."""
+    UNC_COLUMNS), p_bar f32 [S, C], member_nll f32 [S, K] or None (mmu_uncertainty_decompose).
+    inv_temp f32 [K], finite and >= 0: member k's logits are multiplied by inv_temp[k] first
+    (mmu_uncertainty_decompose_scaled); None calls the unscaled symbol."""
     who = "uncertainty_decompose"
     _want(logits, torch.float32, "logits")
     if logits.dim() != 4:
@@ -1248,9 +1271,54 @@ def uncertainty_decompose(logits, y, stats, p_bar, member_nll=None):
         _want(t, torch.float32, name)
         if tuple(t.shape) != shape or not t.is_contiguous():
             raise N.NativeError(f"{who}: {name} must be contiguous f32 {list(shape)}, got {tuple(t.shape)}")
-    _dev_check(logits, y, stats, p_bar, member_nll)
-    N.call("mmu_uncertainty_decompose", _ptr(logits), ss, sk, st, _ptr(y), S, Km, T, C, _ptr(stats), _ptr(p_bar),
-           _ptr(member_nll), _stream(logits))
+    if inv_temp is None:
+        _dev_check(logits, y, stats, p_bar, member_nll)
+        N.call("mmu_uncertainty_decompose", _ptr(logits), ss, sk, st, _ptr(y), S, Km, T, C, _ptr(stats),
+               _ptr(p_bar), _ptr(member_nll), _stream(logits))
+        return
+    _inv_temp_check(who, inv_temp, (Km,), "[K]")
+    _dev_check(logits, y, stats, p_bar, member_nll, inv_temp)
+    N.call("mmu_uncertainty_decompose_scaled", _ptr(logits), ss, sk, st, _ptr(y), S, Km, T, C, _ptr(stats),
+           _ptr(p_bar), _ptr(member_nll), _ptr(inv_temp), _stream(logits))
+
+
+TEMPERATURE_MAX_CANDIDATES = 64   # include/mmu.h mmu_temperature_nll: J <= 64
+
+
+def temperature_nll(logits, y, inv_temp, nll, nll_sum=None):
+    """The ensemble NLL under J candidate inverse-temperature vectors in one read of the logits
+    (mmu_temperature_nll).  logits f32 [S, K, T, C] as uncertainty_decompose takes them, y int64 [S],
+    inv_temp f32 [J, K] (finite, >= 0; J <= 64) -> nll f32 [S, J], nll_sum f64 [J] = sum_s nll[s, j] or
+    None."""
+    who = "temperature_nll"
+    _want(logits, torch.float32, "logits")
+    if logits.dim() != 4:
+        raise N.NativeError(f"{who}: logits must be 4-D [S, K, T, C], got {tuple(logits.shape)}")
+    S, Km, T, C = logits.shape
+    ss, sk, st, sc = logits.stride()
+    if sc != 1 and C > 1:
+        raise N.NativeError(f"{who}: the class axis of logits must be contiguous, got stride {sc}")
+    _want(y, torch.int64, "y")
+    if tuple(y.shape) != (S,) or not y.is_contiguous():
+        raise N.NativeError(f"{who}: y must be contiguous int64 [S] = [{S}], got {tuple(y.shape)}")
+    if inv_temp is None or inv_temp.dim() != 2:
+        raise N.NativeError(f"{who}: inv_temp must be a 2-D f32 [J, K] table")
+    J = inv_temp.shape[0]
+    if not 1 <= J <= TEMPERATURE_MAX_CANDIDATES:
+        raise N.NativeError(f"{who}: J = {J} candidates, must be 1 .. {TEMPERATURE_MAX_CANDIDATES}")
+    _inv_temp_check(who, inv_temp, (J, Km), "[J, K]")
+    if nll is None:
+        raise N.NativeError(f"{who}: nll is required")
+    _want(nll, torch.float32, "nll")
+    if tuple(nll.shape) != (S, J) or not nll.is_contiguous():
+        raise N.NativeError(f"{who}: nll must be contiguous f32 [S, J] = [{S}, {J}], got {tuple(nll.shape)}")
+    if nll_sum is not None:
+        _want(nll_sum, torch.float64, "nll_sum")
+        if tuple(nll_sum.shape) != (J,) or not nll_sum.is_contiguous():
+            raise N.NativeError(f"{who}: nll_sum must be contiguous f64 [J] = [{J}], got {tuple(nll_sum.shape)}")
+    _dev_check(logits, y, inv_temp, nll, nll_sum)
+    N.call("mmu_temperature_nll", _ptr(logits), ss, sk, st, _ptr(y), S, Km, T, C, _ptr(inv_temp), J, _ptr(nll),
+           _ptr(nll_sum), _stream(logits))
 
 
 # include/mmu.h MMU_ROB_*: the columns of robustness_summary's stats

@@ -17,6 +17,8 @@ UncertaintyMeter(decompose=True) (mmu_uncertainty_decompose, the [K, T, B, C] lo
   total = H[p_bar], aleatoric = mean_kt H[p_kt], mi_members = H[p_bar] - mean_k H[p_k],
   mi_passes = mean_k H[p_k] - aleatoric, Brier, vote disagreement, per-member NLL, and the AUROC of
   the uncertainty scores as detectors of the misclassified samples
+UncertaintyMeter(decompose=True, inv_temp=beta) reports the same table for softmax(beta_k z_kt): the
+  ensemble under the temperatures src/calibration.py fits (mmu_uncertainty_decompose_scaled)
 EnsembleMMBT.logits(variant=...) runs the same pass on the img-only / txt-only / control gathers.
 """
 import numpy as np
@@ -182,11 +184,17 @@ def auroc(score, positive):
 class UncertaintyMeter:
     """Accumulates NLL / ECE bins / accuracy over batches with the HIP reduction kernels.
     decompose=True: the entropy / mutual-information split of mmu_uncertainty_decompose as well
-    (per-sample statistics kept on the host; see result())."""
+    (per-sample statistics kept on the host; see result()).
+    inv_temp (decompose=True only): f32 [K] device tensor of inverse temperatures, e.g.
+    calibration.TemperatureScaler.inv_temp(device); member k's logits are multiplied by inv_temp[k]
+    before everything else (mmu_uncertainty_decompose_scaled).  None: the unscaled symbol, as before."""
 
-    def __init__(self, n_bins=15, decompose=False):
+    def __init__(self, n_bins=15, decompose=False, inv_temp=None):
+        if inv_temp is not None and not decompose:
+            raise ValueError("UncertaintyMeter: inv_temp needs decompose=True")
         self.n_bins = n_bins
         self.decompose = decompose
+        self.inv_temp = inv_temp
         self.bins = None
         self.nll_sum = 0.0
         self.correct = 0.0
@@ -227,7 +235,10 @@ class UncertaintyMeter:
         stats = torch.empty(S, K.UNC_NSTAT, dtype=torch.float32, device=dev)
         p_bar = torch.empty(S, C, dtype=torch.float32, device=dev)
         mnll = torch.empty(S, Km, dtype=torch.float32, device=dev)
-        K.uncertainty_decompose(lo, y.long().contiguous(), stats, p_bar, mnll)
+        if self.inv_temp is None:
+            K.uncertainty_decompose(lo, y.long().contiguous(), stats, p_bar, mnll)
+        else:
+            K.uncertainty_decompose(lo, y.long().contiguous(), stats, p_bar, mnll, inv_temp=self.inv_temp)
         col = K.UNC_COLUMNS.index
         nll, cor = stats[:, col("nll")], stats[:, col("correct")]
         self._bin(stats[:, col("conf")].contiguous(), cor.contiguous())
