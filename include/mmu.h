@@ -65,7 +65,7 @@ int mmu_set_seed_offset(const uint64_t* dev_counter);
  *   mmu_uncertainty_decompose launches the same kernel in both modes: it has no atomics, its
  *     sums fold in a fixed lane and wave order, so its result depends on the inputs and the
  *     shape alone and is bitwise repeatable with the mode on or off; mmu_robustness_summary,
- *     mmu_uncertainty_decompose_scaled and mmu_temperature_nll likewise. */
+ *     mmu_uncertainty_decompose_scaled, mmu_temperature_nll and mmu_ensemble_diversity likewise. */
 int mmu_set_deterministic(int on); /* -> the previous value */
 int mmu_get_deterministic(void);
 
@@ -674,6 +674,50 @@ enum {
 int mmu_robustness_summary(const float* logits, int64_t ss, int64_t sv, int64_t sk, const int64_t* y,
                            int64_t S, int64_t V, int64_t K, int64_t C, float* stats, float* per_variant,
                            mmu_stream_t stream);
+
+/* Ensemble diversity, per sample (new symbol, ABI stays 4): which members disagree with which, and by
+ * how much.  The reference's "Prediction Diversity Analysis" (notebooks/analysis_round_1.py:68-113:
+ * mute the true class, keep each sub-network's top-5 probabilities, Kendall tau between two
+ * sub-networks), restated per sample; js and disagree have no counterpart.
+ * logits and y as in mmu_uncertainty_decompose: f32, element (s, k, t, c) at
+ * logits[s*ss + k*sk + t*st + c], class axis contiguous, [K, T, S, C] in place and [S, K, T, C];
+ * y int64 [S].  2 <= K <= 16 members, 1 <= C <= 1024, 0 <= top <= 1024, mute_true 0 / 1.
+ * With p_k = mean_t softmax(logits[s, k, t, :]) and H[q] = -sum_c q_c ln q_c (nats, 0 ln 0 = 0):
+ *   member_arg int32 [S, K] = argmax_c p_k[c], ties to the lowest class.
+ * For each pair (i, j), i < j, in itertools.combinations order, P = K (K - 1) / 2 of them,
+ * pair f32 [S, P, MMU_DIV_NPAIR] holds
+ *   js       = H[(p_i + p_j) / 2] - (H[p_i] + H[p_j]) / 2        (the form of mmu_robustness_summary)
+ *   disagree = 1[member_arg_i != member_arg_j]
+ *   tau      = Kendall tau-b between the truncated vectors x_i and x_j over the C classes.
+ * Truncation (the reference's trunk_pred_top, its quirk included): m = min(top, C); thr_k is the m-th
+ * largest value of p_k over all C classes, counted with multiplicity and with the TRUE CLASS INCLUDED
+ * (the threshold comes from the unmuted row); x_k[c] = p_k[c] if p_k[c] >= thr_k, else 0; then, if
+ * mute_true and 0 <= y < C, x_k[y] = 0.  top = 0: no truncation, every class is kept.  Ties at the
+ * threshold keep every tied class, so more than top classes can be kept (equal logits: all C).
+ * Kendall tau-b over the n0 = C (C - 1) / 2 class pairs a < b, with sx = sign(x_i[a] - x_i[b]) and
+ * sy = sign(x_j[a] - x_j[b]):
+ *   conc = #(sx sy > 0)   disc = #(sx sy < 0)   tx = #(sx = 0)   ty = #(sy = 0)
+ *   tau = (conc - disc) / sqrt((n0 - tx) (n0 - ty)), the quotient formed in f64 and stored as f32;
+ *   NaN when the denominator is 0 (C = 1, or a constant x).  This is scipy.stats.kendalltau's tau-b.
+ * counts int32 [S, P, 4] = (conc, disc, tx, ty), or NULL; each at most 523,776, so exact.
+ * The reference pools all S x C values of two sub-networks into one tau, which mixes the ordering
+ * between samples with the ordering within one; here tau is per sample (average it over the samples
+ * where it is defined).  For one sample the two coincide.
+ * A label outside [0, C) mutes nothing (class indices are compared with y, never indexed by it).
+ * One launch, expf / logf, no atomics, every sum in one fixed order: bitwise repeatable in both
+ * determinism modes.  Refused before any launch: null logits / y / pair / member_arg, non-positive
+ * S / T / C, C > 1024, K < 2, K > 16, top < 0, top > 1024, mute_true not 0 / 1, S over the grid limit
+ * and the stride checks of mmu_uncertainty_decompose. */
+enum {
+  MMU_DIV_JS = 0,
+  MMU_DIV_DISAGREE = 1,
+  MMU_DIV_TAU = 2,
+  MMU_DIV_NPAIR = 3
+};
+int mmu_ensemble_diversity(const float* logits, int64_t ss, int64_t sk, int64_t st, const int64_t* y,
+                           int64_t S, int64_t K, int64_t T, int64_t C, int64_t top, int mute_true,
+                           float* pair /* [S, P, MMU_DIV_NPAIR] */, int32_t* counts /* [S, P, 4] or NULL */,
+                           int32_t* member_arg /* [S, K] */, mmu_stream_t stream);
 
 /* ------------------------------------------------------------------ launch plans
  * What the host would decide for a product -- tiling, tile order, split-K, the split tail rows, the

@@ -1226,4 +1226,29 @@ int mmu_robustness_summary(const float* logits, int64_t ss, int64_t sv, int64_t 
   return check_launch(who);
 }
 
+int mmu_ensemble_diversity(const float* logits, int64_t ss, int64_t sk, int64_t st, const int64_t* y, int64_t S,
+                           int64_t K, int64_t T, int64_t C, int64_t top, int mute_true, float* pair, int32_t* counts,
+                           int32_t* member_arg, mmu_stream_t stream) {
+  const char* who = "mmu_ensemble_diversity";
+  if (!logits) return fail("%s: logits is null", who);
+  if (!y) return fail("%s: y is null", who);
+  if (!pair) return fail("%s: pair is null", who);
+  if (!member_arg) return fail("%s: member_arg is null", who);
+  if (S <= 0) return fail("%s: S = %lld must be positive", who, (long long)S);
+  if (T <= 0) return fail("%s: T = %lld must be positive", who, (long long)T);
+  if (C <= 0) return fail("%s: C = %lld must be positive", who, (long long)C);
+  if (C > 1024) return fail("%s: C = %lld exceeds 1024 classes", who, (long long)C);
+  if (K < 2) return fail("%s: K = %lld is fewer than the 2 members of one pair", who, (long long)K);
+  if (K > 16) return fail("%s: K = %lld exceeds 16 members", who, (long long)K);
+  if (top < 0) return fail("%s: top = %lld must not be negative (0: no truncation)", who, (long long)top);
+  if (top > 1024) return fail("%s: top = %lld exceeds 1024", who, (long long)top);
+  if (mute_true != 0 && mute_true != 1) return fail("%s: mute_true = %d must be 0 or 1", who, mute_true);
+  if (S > 0x7fffffffLL) return fail("%s: S = %lld exceeds the grid limit 2147483647", who, (long long)S);
+  if (check_skt_strides(who, ss, sk, st, S, K, T, C)) return 1;
+  const hipError_t e = ensemble_diversity_launch(logits, ss, sk, st, y, S, K, T, C, top, mute_true, pair, counts,
+                                                 member_arg, (hipStream_t)stream);
+  if (e != hipSuccess) return fail("%s: the LDS request was refused: %s", who, hipGetErrorString(e));
+  return check_launch(who);
+}
+
 }  // extern "C"

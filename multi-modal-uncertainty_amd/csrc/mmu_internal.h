@@ -255,5 +255,9 @@ void temperature_nll_launch(const float* logits, int64_t ss, int64_t sk, int64_t
                             double* nll_sum, hipStream_t s);
 void robustness_summary_launch(const float* logits, int64_t ss, int64_t sv, int64_t sk, const int64_t* y, int64_t S,
                                int64_t V, int64_t K, int64_t C, float* stats, float* per_variant, hipStream_t s);
+// -> hipSuccess, or the error of the dynamic-LDS request (above 64 KiB) that kept the launch from being made
+hipError_t ensemble_diversity_launch(const float* logits, int64_t ss, int64_t sk, int64_t st, const int64_t* y,
+                                     int64_t S, int64_t K, int64_t T, int64_t C, int64_t top, int mute_true,
+                                     float* pair, int32_t* counts, int32_t* member_arg, hipStream_t s);
 
 }  // namespace mmu

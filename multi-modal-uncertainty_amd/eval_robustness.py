@@ -22,6 +22,15 @@ reads the same logits under the fitted temperatures, the metrics gain "calibrate
   <save_path>/uncertainty_<phase>_calibration.json {mode, tau, nll_before, nll_after, passes, rounds,
       at_bound, fit_phase, eval_phase, same_split, before, after}
 is written (before / after: nll, ece, brier, acc, total, mi); the file is itself a valid --temperature.
+With --diversity [--diversity_top 5] [--diversity_keep_true] (at least 2 members) the logits already
+computed also feed a src/diversity.py DiversityMeter, for the full forward and for every --variants entry:
+per pair of members the Jensen-Shannon divergence, the disagreement rate, Kendall's tau-b of the top
+probabilities with the true class muted (--diversity_keep_true: not muted), the double-fault rate, Yule's
+Q and the phi correlation of the members' errors.  The metrics gain "diversity" (and, with other variants,
+"variants_diversity") and
+  <save_path>/uncertainty_<phase>_diversity.json {diversity[, variants_diversity]}
+is written.  --diversity_from LOGITS.npy LABELS.npy runs the meter alone on a saved [S, K, T, C] logits
+file and its labels (the files above) and writes that JSON; no model is built.
 Without --mmbt: the reference's FashionMNIST MIMO robustness pass (eval_robustness.py:42-121,
 BASELINE config 1's model family): each of the 4 quarter-crop views zeroed in turn (the
 weight-sharing model sees the other 3), predictions [4, S, heads, 10] and labels written as
@@ -65,6 +74,12 @@ FLAGS = [
     ("--decompose", dict(action="store_true")),
     ("--variants", dict(nargs="+", default=["full"],
                         choices=["full", "img_only", "txt_only", "control_image", "control_text"])),
+    # MMBT uncertainty mode: pairwise member agreement (src/diversity.py)
+    ("--diversity", dict(action="store_true")),
+    ("--diversity_top", dict(type=int, default=5, help="probabilities each member keeps for Kendall's tau (0: all)")),
+    ("--diversity_keep_true", dict(action="store_true", help="do not mute the true class")),
+    ("--diversity_from", dict(nargs=2, default=None, metavar=("LOGITS.npy", "LABELS.npy"),
+                              help="only the diversity meter, on a saved [S, K, T, C] logits file and its labels")),
     # MMBT uncertainty mode: temperature scaling (src/calibration.py)
     ("--calibrate", dict(type=str, default=None, choices=["shared", "per_member"],
                          help="fit the ensemble's temperature(s) on --calibrate_phase and report --phase under them")),
@@ -118,6 +133,27 @@ def fit_temperature_on(args, ens, loader, dev):
     return scaler
 
 
+def write_diversity(args, blocks):
+    from src.robustness import json_safe
+    os.makedirs(args.save_path, exist_ok=True)
+    with open(os.path.join(args.save_path, f"uncertainty_{args.phase}_diversity.json"), "w") as f:
+        json.dump(json_safe(blocks), f, indent=1, allow_nan=False)
+
+
+def run_diversity_from(args):
+    """--diversity_from: the meter alone on saved logits and labels"""
+    from src.diversity import diversity_from_files
+    if not torch.cuda.is_available():
+        raise RuntimeError("the diversity pass runs on MI355X HIP kernels: no GPU visible")
+    dev = torch.device("cuda:{}".format(args.device))
+    meter = diversity_from_files(args.diversity_from[0], args.diversity_from[1], dev, args.diversity_top,
+                                 not args.diversity_keep_true)
+    blocks = {"diversity": meter.result()}
+    write_diversity(args, blocks)
+    print(json.dumps(blocks))
+    return blocks
+
+
 def run_mmbt(args):
     from src import gin
     from src.mmbt import MultimodalBertClf
@@ -126,6 +162,9 @@ def run_mmbt(args):
     from src.utils import set_seed
     from eval_mmbt_robustness import load_data
     check_calibration_flags(args)
+    if args.diversity:   # refused before the data is read and any model is built
+        from src.diversity import DiversityMeter, check_diversity_flags
+        check_diversity_flags(max(1, len(args.checkpoint_paths or [])), args.diversity_top)
     set_seed(args.seed)
     args.drop_img_percent = 0.0
     data, n_classes, vocab = load_data(args)
@@ -172,6 +211,11 @@ def run_mmbt(args):
         before = meter if decompose else UncertaintyMeter(args.n_bins, decompose=True)
         after = UncertaintyMeter(args.n_bins, decompose=True, inv_temp=inv_temp)
         vafter = {v: UncertaintyMeter(args.n_bins, decompose=True, inv_temp=inv_temp) for v in extra}
+    # --diversity: one more meter per forward, fed from the logits already computed
+    dmeters = {}
+    if args.diversity:
+        dmeters = {v: DiversityMeter(args.diversity_top, not args.diversity_keep_true)
+                   for v in dict.fromkeys(["full"] + extra)}
     all_logits, labels, vlogits = [], [], {v: [] for v in extra}
     with torch.no_grad():
         for x, y in data[args.phase]:
@@ -186,6 +230,8 @@ def run_mmbt(args):
             else:
                 flat = lo.permute(2, 0, 1, 3).reshape(lo.shape[2], -1, lo.shape[3])  # [B, K*T, C]
                 meter.update(flat, y.to(dev))
+            if dmeters:
+                dmeters["full"].update(lo, y.to(dev))
             all_logits.append(lo.permute(2, 0, 1, 3).cpu())
             labels.append(y)
             for v in extra:
@@ -193,6 +239,8 @@ def run_mmbt(args):
                 vmeters[v].update(lv, y.to(dev))
                 if scaler is not None:
                     vafter[v].update(lv, y.to(dev))
+                if dmeters:
+                    dmeters[v].update(lv, y.to(dev))
                 vlogits[v].append(lv.permute(2, 0, 1, 3).cpu())
     full = meter.result()
     res = dict({k: full[k] for k in ("nll", "ece", "acc", "n")}, K=len(members), T=args.mc_samples)
@@ -200,6 +248,14 @@ def run_mmbt(args):
         res["decomposition"] = {k: v for k, v in full.items() if k not in ("nll", "ece", "acc", "n")}
         res["variants"] = {v: full if v == "full" else vmeters[v].result() for v in dict.fromkeys(args.variants)}
     os.makedirs(args.save_path, exist_ok=True)
+    if dmeters:
+        from src.robustness import json_safe
+        blocks = {"diversity": json_safe(dmeters["full"].result())}
+        if extra:
+            blocks["variants_diversity"] = {v: blocks["diversity"] if v == "full" else json_safe(dmeters[v].result())
+                                            for v in dict.fromkeys(args.variants)}
+        res.update(blocks)
+        write_diversity(args, blocks)
     if scaler is not None:
         cal_full = after.result()
         cal = dict(scaler.result, fit_phase=fit_phase, eval_phase=args.phase, same_split=same_split,
@@ -278,6 +334,8 @@ def main(argv=None):
     assert remaining == [], remaining
     from src import gin
     gin.load(args, args.gin_file, args.gin_param)
+    if args.diversity_from:
+        return run_diversity_from(args)
     return run_mmbt(args) if args.mmbt else run_fmnist(args)
 
 

@@ -1359,6 +1359,56 @@ def robustness_summary(logits, y, stats, per_variant=None):
            _stream(logits))
 
 
+# include/mmu.h MMU_DIV_*: the columns of ensemble_diversity's pair table
+DIV_COLUMNS = ("js", "disagree", "tau")
+DIV_NPAIR = len(DIV_COLUMNS)
+DIV_MAX_MEMBERS = 16   # include/mmu.h mmu_ensemble_diversity: 2 <= K <= 16
+DIV_MAX_TOP = 1024     # and 0 <= top <= 1024
+
+
+def ensemble_diversity(logits, y, pair, counts, member_arg, top=5, mute_true=True):
+    """Pairwise member agreement of one batch of the ensemble (mmu_ensemble_diversity).  logits f32
+    [S, K, T, C] as uncertainty_decompose takes them (or [S, K, C]: T = 1, the heads of a head model),
+    y int64 [S] -> pair f32 [S, P, DIV_NPAIR] (columns DIV_COLUMNS; P = K (K - 1) / 2 pairs in
+    itertools.combinations order), counts int32 [S, P, 4] = (conc, disc, tx, ty) or None, member_arg
+    int32 [S, K].  top: the probabilities each member keeps for Kendall's tau (0: all); mute_true: the
+    true class is zeroed first."""
+    who = "ensemble_diversity"
+    _want(logits, torch.float32, "logits")
+    if logits.dim() == 3:
+        logits = logits.unsqueeze(2)
+    if logits.dim() != 4:
+        raise N.NativeError(f"{who}: logits must be 4-D [S, K, T, C] or 3-D [S, K, C], got {tuple(logits.shape)}")
+    S, Km, T, C = logits.shape
+    ss, sk, st, sc = logits.stride()
+    if sc != 1 and C > 1:
+        raise N.NativeError(f"{who}: the class axis of logits must be contiguous, got stride {sc}")
+    if not 2 <= Km <= DIV_MAX_MEMBERS:
+        raise N.NativeError(f"{who}: K = {Km} members, must be 2 .. {DIV_MAX_MEMBERS}")
+    if isinstance(top, bool) or not isinstance(top, int) or not 0 <= top <= DIV_MAX_TOP:
+        raise N.NativeError(f"{who}: top = {top!r} must be an integer 0 .. {DIV_MAX_TOP} (0: no truncation)")
+    if not isinstance(mute_true, (bool, int)) or mute_true not in (0, 1):
+        raise N.NativeError(f"{who}: mute_true = {mute_true!r} must be a bool")
+    _want(y, torch.int64, "y")
+    if tuple(y.shape) != (S,) or not y.is_contiguous():
+        raise N.NativeError(f"{who}: y must be contiguous int64 [S] = [{S}], got {tuple(y.shape)}")
+    P = Km * (Km - 1) // 2
+    for name, t, dt, shape in (("pair", pair, torch.float32, (S, P, DIV_NPAIR)),
+                               ("counts", counts, torch.int32, (S, P, 4)),
+                               ("member_arg", member_arg, torch.int32, (S, Km))):
+        if t is None:
+            if name == "counts":
+                continue
+            raise N.NativeError(f"{who}: {name} is required")
+        _want(t, dt, name)
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise N.NativeError(f"{who}: {name} must be contiguous {str(dt).split('.')[-1]} {list(shape)}, got "
+                                f"{tuple(t.shape)}")
+    _dev_check(logits, y, pair, counts, member_arg)
+    N.call("mmu_ensemble_diversity", _ptr(logits), ss, sk, st, _ptr(y), S, Km, T, C, top, int(mute_true),
+           _ptr(pair), _ptr(counts), _ptr(member_arg), _stream(logits))
+
+
 _alg = {"on": False, "bytes": 0.0, "n": 0}
 
 
