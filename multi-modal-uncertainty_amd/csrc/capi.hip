@@ -1115,16 +1115,21 @@ int mmu_ece_bins(const float* conf, const float* correct, int64_t S, int64_t n_b
   return check_launch("mmu_ece_bins");
 }
 
-// element strides of an [S, K, T, C] logit stack with a contiguous class axis: the axes that step
-// (extent > 1), by ascending stride, must each clear the span of the one below it
-static int check_skt_strides(const char* who, int64_t ss, int64_t sk, int64_t st, int64_t S, int64_t K, int64_t T,
-                             int64_t C) {
-  struct Axis { const char* name; int64_t stride, extent; } ax[3] = {{"ss", ss, S}, {"sk", sk, K}, {"st", st, T}};
+// ---------------------------------------------------------------- the ensemble-statistics entries
+struct StackPtr { const char* name; const void* p; };
+struct StackExtent { const char* name; int64_t v; };
+struct StackAxis { const char* name; int64_t stride, extent; };
+struct StackRange { bool bad; const char* fmt; int64_t v; };  // an entry's own range check; fmt takes who and v
+
+// element strides of a logit stack with a contiguous class axis: the axes that step (extent > 1), by
+// ascending stride, must each clear the span of the one below it
+static int check_skt_strides(const char* who, const StackAxis (&axes)[3], int64_t C) {
+  StackAxis ax[3] = {axes[0], axes[1], axes[2]};
   for (int i = 1; i < 3; ++i)
     for (int j = i; j > 0 && ax[j].stride < ax[j - 1].stride; --j) std::swap(ax[j], ax[j - 1]);
   int64_t span = C;
   const char* below = "C";
-  for (const Axis& a : ax) {
+  for (const StackAxis& a : ax) {
     if (a.extent == 1) continue;
     if (a.stride < span)
       return fail("%s: %s = %lld is smaller than the %lld elements the %s axis below it spans (overlapping layout)",
@@ -1136,20 +1141,33 @@ static int check_skt_strides(const char* who, int64_t ss, int64_t sk, int64_t st
   return 0;
 }
 
-// the refusals mmu_uncertainty_decompose and mmu_uncertainty_decompose_scaled share
+// The refusals of every entry that reads a logit stack, in the order each of them reports: a null
+// pointer, an extent that is not positive, the entry's range checks that come before the class limit,
+// C > 1024, its other range checks, the grid limit of S (the extent of axes[0]), the strides.
+static int stack_check(const char* who, std::initializer_list<StackPtr> ptrs,
+                       std::initializer_list<StackExtent> extents, int64_t C,
+                       std::initializer_list<StackRange> before_classes,
+                       std::initializer_list<StackRange> after_classes, const StackAxis (&axes)[3]) {
+  for (const StackPtr& a : ptrs)
+    if (!a.p) return fail("%s: %s is null", who, a.name);
+  for (const StackExtent& e : extents)
+    if (e.v <= 0) return fail("%s: %s = %lld must be positive", who, e.name, (long long)e.v);
+  for (const StackRange& r : before_classes)
+    if (r.bad) return fail(r.fmt, who, (long long)r.v);
+  if (C > 1024) return fail("%s: C = %lld exceeds 1024 classes", who, (long long)C);
+  for (const StackRange& r : after_classes)
+    if (r.bad) return fail(r.fmt, who, (long long)r.v);
+  const int64_t S = axes[0].extent;
+  if (S > 0x7fffffffLL) return fail("%s: S = %lld exceeds the grid limit 2147483647", who, (long long)S);
+  return check_skt_strides(who, axes, C);
+}
+
+// mmu_uncertainty_decompose and mmu_uncertainty_decompose_scaled
 static int decompose_check(const char* who, const float* logits, int64_t ss, int64_t sk, int64_t st, const int64_t* y,
                            int64_t S, int64_t K, int64_t T, int64_t C, float* stats, float* p_bar) {
-  if (!logits) return fail("%s: logits is null", who);
-  if (!y) return fail("%s: y is null", who);
-  if (!stats) return fail("%s: stats is null", who);
-  if (!p_bar) return fail("%s: p_bar is null", who);
-  if (S <= 0) return fail("%s: S = %lld must be positive", who, (long long)S);
-  if (K <= 0) return fail("%s: K = %lld must be positive", who, (long long)K);
-  if (T <= 0) return fail("%s: T = %lld must be positive", who, (long long)T);
-  if (C <= 0) return fail("%s: C = %lld must be positive", who, (long long)C);
-  if (C > 1024) return fail("%s: C = %lld exceeds 1024 classes", who, (long long)C);
-  if (S > 0x7fffffffLL) return fail("%s: S = %lld exceeds the grid limit 2147483647", who, (long long)S);
-  return check_skt_strides(who, ss, sk, st, S, K, T, C);
+  return stack_check(who, {{"logits", logits}, {"y", y}, {"stats", stats}, {"p_bar", p_bar}},
+                     {{"S", S}, {"K", K}, {"T", T}, {"C", C}}, C, {}, {},
+                     {{"ss", ss, S}, {"sk", sk, K}, {"st", st, T}});
 }
 
 int mmu_uncertainty_decompose(const float* logits, int64_t ss, int64_t sk, int64_t st, const int64_t* y, int64_t S,
@@ -1176,19 +1194,10 @@ int mmu_temperature_nll(const float* logits, int64_t ss, int64_t sk, int64_t st,
                         int64_t K, int64_t T, int64_t C, const float* inv_temp, int64_t J, float* nll,
                         double* nll_sum, mmu_stream_t stream) {
   const char* who = "mmu_temperature_nll";
-  if (!logits) return fail("%s: logits is null", who);
-  if (!y) return fail("%s: y is null", who);
-  if (!inv_temp) return fail("%s: inv_temp is null", who);
-  if (!nll) return fail("%s: nll is null", who);
-  if (S <= 0) return fail("%s: S = %lld must be positive", who, (long long)S);
-  if (K <= 0) return fail("%s: K = %lld must be positive", who, (long long)K);
-  if (T <= 0) return fail("%s: T = %lld must be positive", who, (long long)T);
-  if (C <= 0) return fail("%s: C = %lld must be positive", who, (long long)C);
-  if (J <= 0) return fail("%s: J = %lld must be positive", who, (long long)J);
-  if (C > 1024) return fail("%s: C = %lld exceeds 1024 classes", who, (long long)C);
-  if (J > 64) return fail("%s: J = %lld exceeds 64 candidates", who, (long long)J);
-  if (S > 0x7fffffffLL) return fail("%s: S = %lld exceeds the grid limit 2147483647", who, (long long)S);
-  if (check_skt_strides(who, ss, sk, st, S, K, T, C)) return 1;
+  if (stack_check(who, {{"logits", logits}, {"y", y}, {"inv_temp", inv_temp}, {"nll", nll}},
+                  {{"S", S}, {"K", K}, {"T", T}, {"C", C}, {"J", J}}, C, {},
+                  {{J > 64, "%s: J = %lld exceeds 64 candidates", J}}, {{"ss", ss, S}, {"sk", sk, K}, {"st", st, T}}))
+    return 1;
   temperature_nll_launch(logits, ss, sk, st, y, S, K, T, C, inv_temp, J, nll, nll_sum, (hipStream_t)stream);
   return check_launch(who);
 }
@@ -1196,32 +1205,12 @@ int mmu_temperature_nll(const float* logits, int64_t ss, int64_t sk, int64_t st,
 int mmu_robustness_summary(const float* logits, int64_t ss, int64_t sv, int64_t sk, const int64_t* y, int64_t S,
                            int64_t V, int64_t K, int64_t C, float* stats, float* per_variant, mmu_stream_t stream) {
   const char* who = "mmu_robustness_summary";
-  if (!logits) return fail("%s: logits is null", who);
-  if (!y) return fail("%s: y is null", who);
-  if (!stats) return fail("%s: stats is null", who);
-  if (S <= 0) return fail("%s: S = %lld must be positive", who, (long long)S);
-  if (K <= 0) return fail("%s: K = %lld must be positive", who, (long long)K);
-  if (C <= 0) return fail("%s: C = %lld must be positive", who, (long long)C);
-  if (V < 5) return fail("%s: V = %lld is fewer than the 5 variants of one control repeat (V = 3 + 2n)", who, (long long)V);
-  if (V % 2 == 0) return fail("%s: V = %lld must be odd (V = 3 + 2n)", who, (long long)V);
-  if (V > 1023) return fail("%s: V = %lld exceeds 1023 variants", who, (long long)V);
-  if (C > 1024) return fail("%s: C = %lld exceeds 1024 classes", who, (long long)C);
-  if (S > 0x7fffffffLL) return fail("%s: S = %lld exceeds the grid limit 2147483647", who, (long long)S);
-  // the axes that step (extent > 1), by ascending stride: each must clear the span of the one below it
-  struct Axis { const char* name; int64_t stride, extent; } ax[3] = {{"ss", ss, S}, {"sv", sv, V}, {"sk", sk, K}};
-  for (int i = 1; i < 3; ++i)
-    for (int j = i; j > 0 && ax[j].stride < ax[j - 1].stride; --j) std::swap(ax[j], ax[j - 1]);
-  int64_t span = C;
-  const char* below = "C";
-  for (const Axis& a : ax) {
-    if (a.extent == 1) continue;
-    if (a.stride < span)
-      return fail("%s: %s = %lld is smaller than the %lld elements the %s axis below it spans (overlapping layout)",
-                  who, a.name, (long long)a.stride, (long long)span, below);
-    if (a.stride > INT64_MAX / a.extent) return fail("%s: %s = %lld overflows", who, a.name, (long long)a.stride);
-    span = a.stride * a.extent;
-    below = a.name;
-  }
+  if (stack_check(who, {{"logits", logits}, {"y", y}, {"stats", stats}}, {{"S", S}, {"K", K}, {"C", C}}, C,
+                  {{V < 5, "%s: V = %lld is fewer than the 5 variants of one control repeat (V = 3 + 2n)", V},
+                   {V % 2 == 0, "%s: V = %lld must be odd (V = 3 + 2n)", V},
+                   {V > 1023, "%s: V = %lld exceeds 1023 variants", V}},
+                  {}, {{"ss", ss, S}, {"sv", sv, V}, {"sk", sk, K}}))
+    return 1;
   robustness_summary_launch(logits, ss, sv, sk, y, S, V, K, C, stats, per_variant, (hipStream_t)stream);
   return check_launch(who);
 }
@@ -1230,21 +1219,15 @@ int mmu_ensemble_diversity(const float* logits, int64_t ss, int64_t sk, int64_t 
                            int64_t K, int64_t T, int64_t C, int64_t top, int mute_true, float* pair, int32_t* counts,
                            int32_t* member_arg, mmu_stream_t stream) {
   const char* who = "mmu_ensemble_diversity";
-  if (!logits) return fail("%s: logits is null", who);
-  if (!y) return fail("%s: y is null", who);
-  if (!pair) return fail("%s: pair is null", who);
-  if (!member_arg) return fail("%s: member_arg is null", who);
-  if (S <= 0) return fail("%s: S = %lld must be positive", who, (long long)S);
-  if (T <= 0) return fail("%s: T = %lld must be positive", who, (long long)T);
-  if (C <= 0) return fail("%s: C = %lld must be positive", who, (long long)C);
-  if (C > 1024) return fail("%s: C = %lld exceeds 1024 classes", who, (long long)C);
-  if (K < 2) return fail("%s: K = %lld is fewer than the 2 members of one pair", who, (long long)K);
-  if (K > 16) return fail("%s: K = %lld exceeds 16 members", who, (long long)K);
-  if (top < 0) return fail("%s: top = %lld must not be negative (0: no truncation)", who, (long long)top);
-  if (top > 1024) return fail("%s: top = %lld exceeds 1024", who, (long long)top);
-  if (mute_true != 0 && mute_true != 1) return fail("%s: mute_true = %d must be 0 or 1", who, mute_true);
-  if (S > 0x7fffffffLL) return fail("%s: S = %lld exceeds the grid limit 2147483647", who, (long long)S);
-  if (check_skt_strides(who, ss, sk, st, S, K, T, C)) return 1;
+  if (stack_check(who, {{"logits", logits}, {"y", y}, {"pair", pair}, {"member_arg", member_arg}},
+                  {{"S", S}, {"T", T}, {"C", C}}, C, {},
+                  {{K < 2, "%s: K = %lld is fewer than the 2 members of one pair", K},
+                   {K > 16, "%s: K = %lld exceeds 16 members", K},
+                   {top < 0, "%s: top = %lld must not be negative (0: no truncation)", top},
+                   {top > 1024, "%s: top = %lld exceeds 1024", top},
+                   {mute_true != 0 && mute_true != 1, "%s: mute_true = %lld must be 0 or 1", mute_true}},
+                  {{"ss", ss, S}, {"sk", sk, K}, {"st", st, T}}))
+    return 1;
   const hipError_t e = ensemble_diversity_launch(logits, ss, sk, st, y, S, K, T, C, top, mute_true, pair, counts,
                                                  member_arg, (hipStream_t)stream);
   if (e != hipSuccess) return fail("%s: the LDS request was refused: %s", who, hipGetErrorString(e));

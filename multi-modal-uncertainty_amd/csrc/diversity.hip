@@ -6,22 +6,20 @@
 //
 // One 4-wave block per sample; LDS holds p_k = mean_t softmax(z[s, k, t, :]) of all K members
 // (K rows of C rounded up to 64 floats, dynamic) and three K-entry tables.
-//   Phase 1, the p_k.  For member k the waves share its T rows (wave w takes t = w, w + 4, ...), as in
-//     uncertainty_decompose_kernel: a lane owns classes lane, lane + 64, ..., NJ per lane in registers,
-//     a logit row is loaded once.  The waves' shares are added into the member's LDS row one wave after
-//     the other (wave 0 stores, wave 1 adds, ...; the last one scales by 1 / T): the sum and its order
-//     are those of the decomposition's p_k.
+//   Phase 1, the p_k, by the row scheme of ensemble_rows.h with the waves sharing member k's T rows.
+//     The waves' shares are added into the member's LDS row one wave after the other (wave 0 stores,
+//     wave 1 adds, ...; the last one scales by 1 / T): the sum and its order are those of the
+//     decomposition's p_k.
 //   Phase 2, per member (member k to wave k % 4): H[p_k], the argmax (ties to the lowest class) and
 //     the truncation threshold, the m-th largest p_k[c] counted with multiplicity, by m rounds of a wave
 //     argmax that each retire one class.
-//   Phase 3, per pair (pair q to wave q % 4): the divergence by a wave sum in the form of
-//     robustness_summary_kernel, and the four Kendall counts by a sweep over the class pairs a < b: a
-//     lane keeps the truncated values of its classes a of both members in registers, b walks the classes
-//     (an LDS broadcast), and only the 64-class groups that hold some a < b are visited.  The truncated
-//     vector is never stored: x[c] = p[c] where p[c] >= thr and c is not the muted class, else 0.
-// No atomics, no scratch, one fixed order for every sum and integer counts: the result depends on the
-// inputs and the shape alone (the same launch in both modes of deterministic()).
-#include "mmu_common.h"
+//   Phase 3, per pair (pair q to wave q % 4): the divergence from the entropies by a wave sum, and the
+//     four Kendall counts by a sweep over the class pairs a < b: a lane keeps the truncated values of
+//     its classes a of both members in registers, b walks the classes (an LDS broadcast), and only the
+//     64-class groups that hold some a < b are visited.  The truncated vector is never stored:
+//     x[c] = p[c] where p[c] >= thr and c is not the muted class, else 0.
+// No scratch, and the counts are integers.
+#include "ensemble_rows.h"
 #include "mmu_internal.h"
 
 namespace mmu {
@@ -29,24 +27,6 @@ namespace mmu {
 constexpr int DV_WAVES = 4;
 constexpr int DV_THREADS = 64 * DV_WAVES;
 constexpr int DV_MAXK = 16;
-
-// argmax butterfly: ties go to the lowest class; every lane ends with the same pair
-static __device__ __forceinline__ void dv_wave_argmax(float& best, int& arg) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ob = __shfl_xor(best, o, 64);
-    const int oa = __shfl_xor(arg, o, 64);
-    if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
-  }
-}
-
-static __device__ __forceinline__ int dv_wave_sum_int(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-static __device__ __forceinline__ float dv_xlogx(float p) { return p > 0.f ? p * logf(p) : 0.f; }
 
 // the truncated, muted value of class c
 static __device__ __forceinline__ float dv_keep(float p, float thr, int c, int muted) {
@@ -80,24 +60,8 @@ __global__ __launch_bounds__(DV_THREADS) void ensemble_diversity_kernel(
     for (int64_t t = wave; t < T; t += DV_WAVES) {
       const float* z = logits + s * ss + k * sk + t * st;
       float v[NJ];
-      float mx = -__builtin_huge_valf();
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const int c = lane + 64 * j;
-        v[j] = c < C ? z[c] : -__builtin_huge_valf();
-        mx = fmaxf(mx, v[j]);
-      }
-      mx = wave_max(mx);
-      float se = 0.f;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        v[j] = lane + 64 * j < C ? expf(v[j] - mx) : 0.f;
-        se += v[j];
-      }
-      se = wave_sum(se);
-      const float inv = 1.0f / se;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) acc[j] += v[j] * inv;
+      const float mx = wave_max(load_row<NJ>(z, C, lane, v));
+      softmax_accumulate<NJ>(v, mx, C, lane, acc);
     }
     float* pk = prob + k * CP;
     for (int w = 0; w < nw; ++w) {
@@ -127,11 +91,11 @@ __global__ __launch_bounds__(DV_THREADS) void ensemble_diversity_kernel(
     for (int j = 0; j < NJ; ++j) {
       const int c = lane + 64 * j;
       v[j] = c < C ? pk[c] : -1.f;  // below every probability: never the maximum
-      if (c < C) h -= dv_xlogx(v[j]);
+      if (c < C) h -= xlogx(v[j]);
       if (v[j] > best) { best = v[j]; arg = c; }
     }
     h = wave_sum(h);
-    dv_wave_argmax(best, arg);
+    wave_argmax(best, arg);
     const int amax = arg;
     float thr = 0.f;  // every class is kept
     unsigned gone = 0;  // bit j: class lane + 64 j has been counted
@@ -143,7 +107,7 @@ __global__ __launch_bounds__(DV_THREADS) void ensemble_diversity_kernel(
         const float cand = (gone >> j) & 1u ? -1.f : v[j];
         if (cand > best) { best = cand; arg = lane + 64 * j; }
       }
-      dv_wave_argmax(best, arg);
+      wave_argmax(best, arg);
       thr = best;
       if ((arg & 63) == lane) gone |= 1u << (arg >> 6);
     }
@@ -172,7 +136,7 @@ __global__ __launch_bounds__(DV_THREADS) void ensemble_diversity_kernel(
     for (int j = 0; j < NJ; ++j) {
       const int c = lane + 64 * j;
       const float a = c < C ? pi[c] : 0.f, b = c < C ? pj[c] : 0.f;
-      hm -= dv_xlogx(0.5f * (a + b));
+      hm -= xlogx(0.5f * (a + b));
       xi[j] = dv_keep(a, thr_i, c, muted);
       xj[j] = dv_keep(b, thr_j, c, muted);
     }
@@ -195,14 +159,14 @@ __global__ __launch_bounds__(DV_THREADS) void ensemble_diversity_kernel(
     }
     // (kept per lane: forming the four counts from lane masks and scalar population counts was
     // measured slower at C = 1024, 22.4 ms against 15.1 ms for S = 5000, K = 5, and no faster at C = 101)
-    conc = dv_wave_sum_int(conc);
-    disc = dv_wave_sum_int(disc);
-    tx = dv_wave_sum_int(tx);
-    ty = dv_wave_sum_int(ty);
+    conc = wave_sum_int(conc);
+    disc = wave_sum_int(disc);
+    tx = wave_sum_int(tx);
+    ty = wave_sum_int(ty);
     if (lane == 0) {
       const int64_t row = s * P + q;
       float* o = pair + row * MMU_DIV_NPAIR;
-      o[MMU_DIV_JS] = (float)((double)hm - 0.5 * ((double)t_ent[i] + (double)t_ent[jm]));
+      o[MMU_DIV_JS] = js_from_entropies(hm, t_ent[i], t_ent[jm]);
       o[MMU_DIV_DISAGREE] = t_arg[i] != t_arg[jm] ? 1.f : 0.f;
       const int64_t dx = n0 - tx, dy = n0 - ty;
       o[MMU_DIV_TAU] = dx > 0 && dy > 0 ? (float)((double)(conc - disc) / sqrt((double)(dx * dy)))
@@ -227,23 +191,17 @@ hipError_t ensemble_diversity_launch(const float* logits, int64_t ss, int64_t sk
                                      int64_t S, int64_t K, int64_t T, int64_t C, int64_t top, int mute_true,
                                      float* pair, int32_t* counts, int32_t* member_arg, hipStream_t s) {
   const int64_t lds = ensemble_diversity_lds_bytes(K, C);
-#define MMU_DV_LAUNCH(NJ)                                                                                          \
-  do {                                                                                                             \
-    if (lds > 65536) {                                                                                             \
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ensemble_diversity_kernel<NJ>),     \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);              \
-      if (e != hipSuccess) return e;                                                                               \
-    }                                                                                                              \
-    hipLaunchKernelGGL(ensemble_diversity_kernel<NJ>, dim3((unsigned)S), dim3(DV_THREADS), (size_t)lds, s, logits, \
-                       ss, sk, st, y, (int)K, T, (int)C, (int)top, mute_true, pair, counts, member_arg);           \
-  } while (0)
-  if (C <= 64) MMU_DV_LAUNCH(1);
-  else if (C <= 128) MMU_DV_LAUNCH(2);
-  else if (C <= 256) MMU_DV_LAUNCH(4);
-  else if (C <= 512) MMU_DV_LAUNCH(8);
-  else MMU_DV_LAUNCH(16);
-#undef MMU_DV_LAUNCH
-  return hipSuccess;
+  return dispatch_nj(C, [&](auto nj) {
+    constexpr int NJ = decltype(nj)::value;
+    if (lds > 65536) {
+      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ensemble_diversity_kernel<NJ>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(ensemble_diversity_kernel<NJ>, dim3((unsigned)S), dim3(DV_THREADS), (size_t)lds, s, logits, ss,
+                       sk, st, y, (int)K, T, (int)C, (int)top, mute_true, pair, counts, member_arg);
+    return hipSuccess;
+  });
 }
 
 }  // namespace mmu

@@ -4,15 +4,13 @@
 // notebooks/utils.py: label probability per variant, experimental shift against the mean control
 // shift, argmax of the head-mean logits), restated; the Jensen-Shannon columns have no counterpart.
 //
-// One 4-wave block per sample.  A wave reduces a whole variant: a lane owns classes lane, lane + 64,
-// ..., NJ per lane (NJ * 64 >= C, NJ <= 16) in registers, every logit row is loaded once, and the
-// row's softmax share of p_v and its share of the head-sum logits come from those registers.  Wave 0
+// The row scheme of ensemble_rows.h, but a wave reduces a whole variant (its K head rows): the
+// row's softmax share of p_v and its share of the head-sum logits come from the row's registers.  Wave 0
 // reduces variant 0 first and parks p_0 and H[p_0] in LDS; after one barrier wave w takes variants
 // 1 + w, 5 + w, ... and forms each one's label probability, hit and divergence from p_0.  The
 // per-variant triples meet in LDS, and threads 0 / 1 fold the image / text controls in index order
-// (means, and the std as a two-pass sum, in f64).  No atomics: every sum has one fixed order, so the
-// result depends on the inputs and the shape alone (the same launch in both modes of deterministic()).
-#include "mmu_common.h"
+// (means, and the std as a two-pass sum, in f64).
+#include "ensemble_rows.h"
 #include "mmu_internal.h"
 
 namespace mmu {
@@ -20,18 +18,6 @@ namespace mmu {
 constexpr int RS_WAVES = 4;
 constexpr int RS_THREADS = 64 * RS_WAVES;
 constexpr int RS_MAXV = 1023;
-
-// argmax butterfly: ties go to the lowest class; every lane ends with the same pair
-static __device__ __forceinline__ void rs_wave_argmax(float& best, int& arg) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ob = __shfl_xor(best, o, 64);
-    const int oa = __shfl_xor(arg, o, 64);
-    if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
-  }
-}
-
-static __device__ __forceinline__ float rs_xlogx(float p) { return p > 0.f ? p * logf(p) : 0.f; }
 
 // p_v = mean_k softmax(z[k, :]) in p[] (0 past C), zs[] = sum_k z[k, :] (-inf past C)
 template <int NJ>
@@ -43,27 +29,12 @@ static __device__ __forceinline__ void rs_reduce_variant(const float* __restrict
     zs[j] = lane + 64 * j < C ? 0.f : -__builtin_huge_valf();
   }
   for (int64_t k = 0; k < K; ++k) {
-    const float* row = z + k * sk;
     float v[NJ];
-    float mx = -__builtin_huge_valf();
+    const float mx = wave_max(load_row<NJ>(z + k * sk, C, lane, v));
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      const int c = lane + 64 * j;
-      v[j] = c < C ? row[c] : -__builtin_huge_valf();
-      mx = fmaxf(mx, v[j]);
-    }
-    mx = wave_max(mx);
-    float se = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
+    for (int j = 0; j < NJ; ++j)
       if (lane + 64 * j < C) zs[j] += v[j];
-      v[j] = lane + 64 * j < C ? expf(v[j] - mx) : 0.f;
-      se += v[j];
-    }
-    se = wave_sum(se);
-    const float inv = 1.0f / se;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) p[j] += v[j] * inv;
+    softmax_accumulate<NJ>(v, mx, C, lane, p);
   }
   const float invK = 1.0f / (float)K;
 #pragma unroll
@@ -85,10 +56,10 @@ static __device__ __forceinline__ void rs_variant_stats(const float (&p)[NJ], co
       const float zm = zs[j] * invK;
       if (zm > best) { best = zm; arg = c; }
       if ((int64_t)c == yy) py = p[j];
-      h -= rs_xlogx(p[j]);
+      h -= xlogx(p[j]);
     }
   }
-  rs_wave_argmax(best, arg);
+  wave_argmax(best, arg);
   pl = wave_sum(py);  // one owner, the others hold 0
   ent = wave_sum(h);
   hit = (int64_t)arg == yy ? 1.f : 0.f;
@@ -129,11 +100,11 @@ __global__ __launch_bounds__(RS_THREADS) void robustness_summary_kernel(
     float hm = 0.f;
 #pragma unroll
     for (int j = 0; j < NJ; ++j)
-      if (lane + 64 * j < C) hm -= rs_xlogx(0.5f * (p[j] + p0[lane + 64 * j]));
+      if (lane + 64 * j < C) hm -= xlogx(0.5f * (p[j] + p0[lane + 64 * j]));
     hm = wave_sum(hm);
     if (lane == 0) {
       t_pl[v] = pl;
-      t_js[v] = (float)((double)hm - 0.5 * ((double)ent + (double)ent0));
+      t_js[v] = js_from_entropies(hm, ent, ent0);
       t_hit[v] = hit;
     }
   }
@@ -180,15 +151,10 @@ __global__ __launch_bounds__(RS_THREADS) void robustness_summary_kernel(
 
 void robustness_summary_launch(const float* logits, int64_t ss, int64_t sv, int64_t sk, const int64_t* y, int64_t S,
                                int64_t V, int64_t K, int64_t C, float* stats, float* per_variant, hipStream_t s) {
-#define MMU_RS_LAUNCH(NJ)                                                                                      \
-  hipLaunchKernelGGL(robustness_summary_kernel<NJ>, dim3((unsigned)S), dim3(RS_THREADS), 0, s, logits, ss, sv, \
-                     sk, y, V, K, C, stats, per_variant)
-  if (C <= 64) MMU_RS_LAUNCH(1);
-  else if (C <= 128) MMU_RS_LAUNCH(2);
-  else if (C <= 256) MMU_RS_LAUNCH(4);
-  else if (C <= 512) MMU_RS_LAUNCH(8);
-  else MMU_RS_LAUNCH(16);
-#undef MMU_RS_LAUNCH
+  dispatch_nj(C, [&](auto nj) {
+    hipLaunchKernelGGL(robustness_summary_kernel<decltype(nj)::value>, dim3((unsigned)S), dim3(RS_THREADS), 0, s,
+                       logits, ss, sv, sk, y, V, K, C, stats, per_variant);
+  });
 }
 
 }  // namespace mmu

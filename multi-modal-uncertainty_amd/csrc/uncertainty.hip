@@ -3,7 +3,7 @@
 // North-star metrics.  Convention of the reference analysis code:
 // softmax per member / pass, then the mean over members (notebooks/food101_robustness.py:25-36,
 // notebooks/utils.py:22-23).  One 128-thread block per sample reduces R = K*T logit rows.
-#include "mmu_common.h"
+#include "ensemble_rows.h"
 #include "mmu_internal.h"
 
 namespace mmu {
@@ -121,26 +121,13 @@ void ece_bins_launch(const float* conf, const float* correct, int64_t S, int64_t
 }
 
 // ------------------------------------------------------------------ entropy / mutual-information split
-// One 4-wave block per sample.  For member k the waves share its T rows (wave w takes t = w, w + 4,
-// ...).  A lane owns classes lane, lane + 64, ..., NJ per lane (NJ * 64 >= C, NJ <= 16) in registers:
-// a logit row is loaded once, and its max / argmax vote, exp-sum, entropy ln Z - sum e^(z-m) (z-m) / Z
-// and its share of the member's p_k all come from those registers.  The waves' partial p_k meet in
-// LDS and are folded in wave order by the thread that owns the class (tid, tid + 256, ...), which
-// also keeps that class of p = mean_k p_k.  No atomics: every sum has one fixed order, so the result
-// depends on the inputs and the shape alone (the same launch in both modes of deterministic()).
-// The per-row and per-member entropies are summed over rows / members in f64 (a handful of adds).
+// The row scheme of ensemble_rows.h, the waves sharing member k's T rows.  Beside its share of the
+// member's p_k a row gives its argmax vote and its entropy ln Z - sum e^(z-m) (z-m) / Z.  The waves'
+// partial p_k meet in LDS and are folded in wave order by the thread that owns the class (tid,
+// tid + 256, ...), which also keeps that class of p = mean_k p_k.  The per-row and per-member
+// entropies are summed over rows / members in f64 (a handful of adds).
 constexpr int UD_WAVES = 4;
 constexpr int UD_THREADS = 64 * UD_WAVES;
-
-// argmax butterfly: ties go to the lowest class; every lane ends with the same pair
-static __device__ __forceinline__ void wave_argmax(float& best, int& arg) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ob = __shfl_xor(best, o, 64);
-    const int oa = __shfl_xor(arg, o, 64);
-    if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
-  }
-}
 
 // SCALED (mmu_uncertainty_decompose_scaled): member k's logits are multiplied by inv_temp[k] as they
 // are loaded, and everything below sees beta_k z_kt; the unscaled instantiation never reads inv_temp.
@@ -175,6 +162,8 @@ __global__ __launch_bounds__(UD_THREADS) void uncertainty_decompose_kernel(
     if constexpr (SCALED) beta = inv_temp[k];
     for (int64_t t = wave; t < T; t += UD_WAVES) {
       const float* z = logits + s * ss + k * sk + t * st;
+      // load_row and softmax_accumulate written out, with the scale, the argmax, the entropy term sum e d
+      // and the vote in their loops: on the helpers NJ = 16 takes 129 VGPRs for 117 and loses a wave
       float v[NJ];
       float best = -__builtin_huge_valf();
       int arg = lane;
@@ -300,21 +289,15 @@ __global__ __launch_bounds__(UD_THREADS) void uncertainty_decompose_kernel(
 void uncertainty_decompose_launch(const float* logits, int64_t ss, int64_t sk, int64_t st, const int64_t* y, int64_t S,
                                   int64_t K, int64_t T, int64_t C, float* stats, float* p_bar, float* member_nll,
                                   const float* inv_temp, hipStream_t s) {
-#define MMU_UD_LAUNCH(NJ)                                                                                      \
-  do {                                                                                                         \
-    if (inv_temp)                                                                                              \
-      hipLaunchKernelGGL((uncertainty_decompose_kernel<NJ, true>), dim3((unsigned)S), dim3(UD_THREADS), 0, s, \
-                         logits, ss, sk, st, y, K, T, C, stats, p_bar, member_nll, inv_temp);                  \
-    else                                                                                                       \
-      hipLaunchKernelGGL((uncertainty_decompose_kernel<NJ, false>), dim3((unsigned)S), dim3(UD_THREADS), 0, s, \
-                         logits, ss, sk, st, y, K, T, C, stats, p_bar, member_nll, inv_temp);                  \
-  } while (0)
-  if (C <= 64) MMU_UD_LAUNCH(1);
-  else if (C <= 128) MMU_UD_LAUNCH(2);
-  else if (C <= 256) MMU_UD_LAUNCH(4);
-  else if (C <= 512) MMU_UD_LAUNCH(8);
-  else MMU_UD_LAUNCH(16);
-#undef MMU_UD_LAUNCH
+  dispatch_nj(C, [&](auto nj) {
+    constexpr int NJ = decltype(nj)::value;
+    if (inv_temp)
+      hipLaunchKernelGGL((uncertainty_decompose_kernel<NJ, true>), dim3((unsigned)S), dim3(UD_THREADS), 0, s, logits,
+                         ss, sk, st, y, K, T, C, stats, p_bar, member_nll, inv_temp);
+    else
+      hipLaunchKernelGGL((uncertainty_decompose_kernel<NJ, false>), dim3((unsigned)S), dim3(UD_THREADS), 0, s, logits,
+                         ss, sk, st, y, K, T, C, stats, p_bar, member_nll, inv_temp);
+  });
 }
 
 }  // namespace mmu

@@ -1245,6 +1245,43 @@ def _inv_temp_check(who, inv_temp, shape, what):
     _inv_temp_seen = (weakref.ref(inv_temp), inv_temp._version)
 
 
+def _labels(who, y, S):
+    _want(y, torch.int64, "y")
+    if tuple(y.shape) != (S,) or not y.is_contiguous():
+        raise N.NativeError(f"{who}: y must be contiguous int64 [S] = [{S}], got {tuple(y.shape)}")
+
+
+def _logit_stack(who, logits, y, axes, allow_3d=False):
+    """The logit stack of an ensemble statistic: f32, 4-D with the axes named (3-D where allowed: the third
+    axis is added with extent 1), any strides with a contiguous class axis; y contiguous int64 [S] (None:
+    the caller checks the labels later, with _labels) -> the 4-D view, its four extents, its three strides."""
+    _want(logits, torch.float32, "logits")
+    if allow_3d and logits.dim() == 3:
+        logits = logits.unsqueeze(2)
+    if logits.dim() != 4:
+        ax = axes.split(", ")
+        alt = f" or 3-D [{', '.join(ax[:2] + ax[3:])}]" if allow_3d else ""
+        raise N.NativeError(f"{who}: logits must be 4-D [{axes}]{alt}, got {tuple(logits.shape)}")
+    *strides, sc = logits.stride()
+    if sc != 1 and logits.shape[3] > 1:
+        raise N.NativeError(f"{who}: the class axis of logits must be contiguous, got stride {sc}")
+    if y is not None:
+        _labels(who, y, logits.shape[0])
+    return logits, tuple(logits.shape), strides
+
+
+def _out_tensor(who, name, t, dtype, shape, required=True, what=None):
+    """An output tensor: None only where it is not required, else the dtype, the shape, contiguous.
+    what: how the message words dtype and shape (default: 'f32' and the shape as a list)."""
+    if t is None:
+        if required:
+            raise N.NativeError(f"{who}: {name} is required")
+        return
+    _want(t, dtype, name)
+    if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise N.NativeError(f"{who}: {name} must be contiguous {what or f'f32 {list(shape)}'}, got {tuple(t.shape)}")
+
+
 def uncertainty_decompose(logits, y, stats, p_bar, member_nll=None, inv_temp=None):
     """logits f32 [S, K, T, C], any strides with a contiguous class axis (``lo.permute(2, 0, 1, 3)`` of the
     [K, T, B, C] ensemble logits is read in place), y int64 [S] -> stats f32 [S, UNC_NSTAT] (columns
@@ -1252,25 +1289,10 @@ def uncertainty_decompose(logits, y, stats, p_bar, member_nll=None, inv_temp=Non
     inv_temp f32 [K], finite and >= 0: member k's logits are multiplied by inv_temp[k] first
     (mmu_uncertainty_decompose_scaled); None calls the unscaled symbol."""
     who = "uncertainty_decompose"
-    _want(logits, torch.float32, "logits")
-    if logits.dim() != 4:
-        raise N.NativeError(f"{who}: logits must be 4-D [S, K, T, C], got {tuple(logits.shape)}")
-    S, Km, T, C = logits.shape
-    ss, sk, st, sc = logits.stride()
-    if sc != 1 and C > 1:
-        raise N.NativeError(f"{who}: the class axis of logits must be contiguous, got stride {sc}")
-    _want(y, torch.int64, "y")
-    if tuple(y.shape) != (S,) or not y.is_contiguous():
-        raise N.NativeError(f"{who}: y must be contiguous int64 [S] = [{S}], got {tuple(y.shape)}")
-    for name, t, shape in (("stats", stats, (S, UNC_NSTAT)), ("p_bar", p_bar, (S, C)),
-                           ("member_nll", member_nll, (S, Km))):
-        if t is None:
-            if name == "member_nll":
-                continue
-            raise N.NativeError(f"{who}: {name} is required")
-        _want(t, torch.float32, name)
-        if tuple(t.shape) != shape or not t.is_contiguous():
-            raise N.NativeError(f"{who}: {name} must be contiguous f32 {list(shape)}, got {tuple(t.shape)}")
+    logits, (S, Km, T, C), (ss, sk, st) = _logit_stack(who, logits, y, "S, K, T, C")
+    _out_tensor(who, "stats", stats, torch.float32, (S, UNC_NSTAT))
+    _out_tensor(who, "p_bar", p_bar, torch.float32, (S, C))
+    _out_tensor(who, "member_nll", member_nll, torch.float32, (S, Km), required=False)
     if inv_temp is None:
         _dev_check(logits, y, stats, p_bar, member_nll)
         N.call("mmu_uncertainty_decompose", _ptr(logits), ss, sk, st, _ptr(y), S, Km, T, C, _ptr(stats),
@@ -1291,31 +1313,15 @@ def temperature_nll(logits, y, inv_temp, nll, nll_sum=None):
     inv_temp f32 [J, K] (finite, >= 0; J <= 64) -> nll f32 [S, J], nll_sum f64 [J] = sum_s nll[s, j] or
     None."""
     who = "temperature_nll"
-    _want(logits, torch.float32, "logits")
-    if logits.dim() != 4:
-        raise N.NativeError(f"{who}: logits must be 4-D [S, K, T, C], got {tuple(logits.shape)}")
-    S, Km, T, C = logits.shape
-    ss, sk, st, sc = logits.stride()
-    if sc != 1 and C > 1:
-        raise N.NativeError(f"{who}: the class axis of logits must be contiguous, got stride {sc}")
-    _want(y, torch.int64, "y")
-    if tuple(y.shape) != (S,) or not y.is_contiguous():
-        raise N.NativeError(f"{who}: y must be contiguous int64 [S] = [{S}], got {tuple(y.shape)}")
+    logits, (S, Km, T, C), (ss, sk, st) = _logit_stack(who, logits, y, "S, K, T, C")
     if inv_temp is None or inv_temp.dim() != 2:
         raise N.NativeError(f"{who}: inv_temp must be a 2-D f32 [J, K] table")
     J = inv_temp.shape[0]
     if not 1 <= J <= TEMPERATURE_MAX_CANDIDATES:
         raise N.NativeError(f"{who}: J = {J} candidates, must be 1 .. {TEMPERATURE_MAX_CANDIDATES}")
     _inv_temp_check(who, inv_temp, (J, Km), "[J, K]")
-    if nll is None:
-        raise N.NativeError(f"{who}: nll is required")
-    _want(nll, torch.float32, "nll")
-    if tuple(nll.shape) != (S, J) or not nll.is_contiguous():
-        raise N.NativeError(f"{who}: nll must be contiguous f32 [S, J] = [{S}, {J}], got {tuple(nll.shape)}")
-    if nll_sum is not None:
-        _want(nll_sum, torch.float64, "nll_sum")
-        if tuple(nll_sum.shape) != (J,) or not nll_sum.is_contiguous():
-            raise N.NativeError(f"{who}: nll_sum must be contiguous f64 [J] = [{J}], got {tuple(nll_sum.shape)}")
+    _out_tensor(who, "nll", nll, torch.float32, (S, J), what=f"f32 [S, J] = [{S}, {J}]")
+    _out_tensor(who, "nll_sum", nll_sum, torch.float64, (J,), required=False, what=f"f64 [J] = [{J}]")
     _dev_check(logits, y, inv_temp, nll, nll_sum)
     N.call("mmu_temperature_nll", _ptr(logits), ss, sk, st, _ptr(y), S, Km, T, C, _ptr(inv_temp), J, _ptr(nll),
            _ptr(nll_sum), _stream(logits))
@@ -1334,26 +1340,9 @@ def robustness_summary(logits, y, stats, per_variant=None):
     -> stats f32 [S, ROB_NSTAT] (columns ROB_COLUMNS), per_variant f32 [S, 3, V] = (p_label, js, hit) or
     None (mmu_robustness_summary)."""
     who = "robustness_summary"
-    _want(logits, torch.float32, "logits")
-    if logits.dim() == 3:
-        logits = logits.unsqueeze(2)
-    if logits.dim() != 4:
-        raise N.NativeError(f"{who}: logits must be 4-D [S, V, K, C] or 3-D [S, V, C], got {tuple(logits.shape)}")
-    S, V, Km, C = logits.shape
-    ss, sv, sk, sc = logits.stride()
-    if sc != 1 and C > 1:
-        raise N.NativeError(f"{who}: the class axis of logits must be contiguous, got stride {sc}")
-    _want(y, torch.int64, "y")
-    if tuple(y.shape) != (S,) or not y.is_contiguous():
-        raise N.NativeError(f"{who}: y must be contiguous int64 [S] = [{S}], got {tuple(y.shape)}")
-    for name, t, shape in (("stats", stats, (S, ROB_NSTAT)), ("per_variant", per_variant, (S, 3, V))):
-        if t is None:
-            if name == "per_variant":
-                continue
-            raise N.NativeError(f"{who}: {name} is required")
-        _want(t, torch.float32, name)
-        if tuple(t.shape) != shape or not t.is_contiguous():
-            raise N.NativeError(f"{who}: {name} must be contiguous f32 {list(shape)}, got {tuple(t.shape)}")
+    logits, (S, V, Km, C), (ss, sv, sk) = _logit_stack(who, logits, y, "S, V, K, C", allow_3d=True)
+    _out_tensor(who, "stats", stats, torch.float32, (S, ROB_NSTAT))
+    _out_tensor(who, "per_variant", per_variant, torch.float32, (S, 3, V), required=False)
     _dev_check(logits, y, stats, per_variant)
     N.call("mmu_robustness_summary", _ptr(logits), ss, sv, sk, _ptr(y), S, V, Km, C, _ptr(stats), _ptr(per_variant),
            _stream(logits))
@@ -1374,36 +1363,18 @@ def ensemble_diversity(logits, y, pair, counts, member_arg, top=5, mute_true=Tru
     int32 [S, K].  top: the probabilities each member keeps for Kendall's tau (0: all); mute_true: the
     true class is zeroed first."""
     who = "ensemble_diversity"
-    _want(logits, torch.float32, "logits")
-    if logits.dim() == 3:
-        logits = logits.unsqueeze(2)
-    if logits.dim() != 4:
-        raise N.NativeError(f"{who}: logits must be 4-D [S, K, T, C] or 3-D [S, K, C], got {tuple(logits.shape)}")
-    S, Km, T, C = logits.shape
-    ss, sk, st, sc = logits.stride()
-    if sc != 1 and C > 1:
-        raise N.NativeError(f"{who}: the class axis of logits must be contiguous, got stride {sc}")
+    logits, (S, Km, T, C), (ss, sk, st) = _logit_stack(who, logits, None, "S, K, T, C", allow_3d=True)
     if not 2 <= Km <= DIV_MAX_MEMBERS:
         raise N.NativeError(f"{who}: K = {Km} members, must be 2 .. {DIV_MAX_MEMBERS}")
     if isinstance(top, bool) or not isinstance(top, int) or not 0 <= top <= DIV_MAX_TOP:
         raise N.NativeError(f"{who}: top = {top!r} must be an integer 0 .. {DIV_MAX_TOP} (0: no truncation)")
     if not isinstance(mute_true, (bool, int)) or mute_true not in (0, 1):
         raise N.NativeError(f"{who}: mute_true = {mute_true!r} must be a bool")
-    _want(y, torch.int64, "y")
-    if tuple(y.shape) != (S,) or not y.is_contiguous():
-        raise N.NativeError(f"{who}: y must be contiguous int64 [S] = [{S}], got {tuple(y.shape)}")
+    _labels(who, y, S)
     P = Km * (Km - 1) // 2
-    for name, t, dt, shape in (("pair", pair, torch.float32, (S, P, DIV_NPAIR)),
-                               ("counts", counts, torch.int32, (S, P, 4)),
-                               ("member_arg", member_arg, torch.int32, (S, Km))):
-        if t is None:
-            if name == "counts":
-                continue
-            raise N.NativeError(f"{who}: {name} is required")
-        _want(t, dt, name)
-        if tuple(t.shape) != shape or not t.is_contiguous():
-            raise N.NativeError(f"{who}: {name} must be contiguous {str(dt).split('.')[-1]} {list(shape)}, got "
-                                f"{tuple(t.shape)}")
+    _out_tensor(who, "pair", pair, torch.float32, (S, P, DIV_NPAIR), what=f"float32 {[S, P, DIV_NPAIR]}")
+    _out_tensor(who, "counts", counts, torch.int32, (S, P, 4), required=False, what=f"int32 {[S, P, 4]}")
+    _out_tensor(who, "member_arg", member_arg, torch.int32, (S, Km), what=f"int32 {[S, Km]}")
     _dev_check(logits, y, pair, counts, member_arg)
     N.call("mmu_ensemble_diversity", _ptr(logits), ss, sk, st, _ptr(y), S, Km, T, C, top, int(mute_true),
            _ptr(pair), _ptr(counts), _ptr(member_arg), _stream(logits))
