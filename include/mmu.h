@@ -65,7 +65,9 @@ int mmu_set_seed_offset(const uint64_t* dev_counter);
  *   mmu_uncertainty_decompose launches the same kernel in both modes: it has no atomics, its
  *     sums fold in a fixed lane and wave order, so its result depends on the inputs and the
  *     shape alone and is bitwise repeatable with the mode on or off; mmu_robustness_summary,
- *     mmu_uncertainty_decompose_scaled, mmu_temperature_nll and mmu_ensemble_diversity likewise. */
+ *     mmu_uncertainty_decompose_scaled, mmu_temperature_nll and mmu_ensemble_diversity likewise;
+ *     mmu_rank_table too launches one thing in both modes: it adds no float anywhere, and its column
+ *     sums are 64-bit integer atomic adds, whose result does not depend on their order. */
 int mmu_set_deterministic(int on); /* -> the previous value */
 int mmu_get_deterministic(void);
 
@@ -718,6 +720,34 @@ int mmu_ensemble_diversity(const float* logits, int64_t ss, int64_t sk, int64_t 
                            int64_t S, int64_t K, int64_t T, int64_t C, int64_t top, int mute_true,
                            float* pair /* [S, P, MMU_DIV_NPAIR] */, int32_t* counts /* [S, P, 4] or NULL */,
                            int32_t* member_arg /* [S, K] */, mmu_stream_t stream);
+
+/* Exact rank table over J score columns (new symbol, ABI stays 4): the integers every ranking metric
+ * is a function of -- the AUC table and the epoch-ensemble AUC of the reference's
+ * notebooks/hatefulmeme_robustness.py (AUC_table, ensemble_overtime), the AUROC of an uncertainty score
+ * and its risk-coverage area.  The host forms each figure in fp64 from them (src/ranking.py), so a
+ * result depends on the scores alone, not on summation order, launch shape or determinism mode.
+ * Score (s, j) is x[s*ss + j*sj], f32, element strides: a contiguous [S, J] table and a [J, S] table
+ * are both read in place.  group uint8 [S], contiguous: non-zero marks group 1 (the positives, or the
+ * wrong samples), zero group 0.
+ * rank int32 [J, S, MMU_RANK_NRANK], or NULL: for column j and sample i, comparing as IEEE f32,
+ *   lt_g = #{i' in group g : x[i', j] <  x[i, j]}
+ *   eq_g = #{i' in group g : x[i', j] == x[i, j]}, sample i itself included.
+ * So -0 ties +0, +-inf are ordinary values, subnormals are distinct values (nothing is flushed), and a
+ * NaN sample has all four counts 0 and is counted by nobody.
+ * counts int64 [J, MMU_RANK_NCOUNT]: nan = the NaN scores of the column; n1, n0 = the non-NaN samples
+ * per group; gt = sum over group 1 of lt_0 (the (positive, negative) pairs with the positive strictly
+ * higher); eq = sum over group 1 of eq_0.  AUROC = (gt + eq / 2) / (n1 n0).
+ * A count is at most S, a count sum at most S^2.  Every output element is written.
+ * One sweep of S^2 compares per column: blocks of MMU_RANK_BLOCK_ROWS samples, the column streamed
+ * through LDS in tiles of MMU_RANK_TILE candidates.  Refused before any launch: null x / group /
+ * counts; non-positive S / J; S > 2^20 (the sweep is O(S^2) per column); J > 65535; a stride <= 0 on an
+ * axis of extent > 1; overlapping axes (the larger stride must clear extent x the smaller); x or rank
+ * not 4-byte aligned, counts not 8-byte aligned. */
+enum { MMU_RANK_LT0 = 0, MMU_RANK_EQ0 = 1, MMU_RANK_LT1 = 2, MMU_RANK_EQ1 = 3, MMU_RANK_NRANK = 4 };
+enum { MMU_RANK_N1 = 0, MMU_RANK_N0 = 1, MMU_RANK_GT = 2, MMU_RANK_EQ = 3, MMU_RANK_NAN = 4, MMU_RANK_NCOUNT = 5 };
+enum { MMU_RANK_BLOCK_ROWS = 1024, MMU_RANK_TILE = 1024, MMU_RANK_MAX_S = 1 << 20, MMU_RANK_MAX_J = 65535 };
+int mmu_rank_table(const float* x, int64_t ss, int64_t sj, const uint8_t* group, int64_t S, int64_t J,
+                   int32_t* rank /* [J, S, 4] or NULL */, int64_t* counts /* [J, 5] */, mmu_stream_t stream);
 
 /* ------------------------------------------------------------------ launch plans
  * What the host would decide for a product -- tiling, tile order, split-K, the split tail rows, the

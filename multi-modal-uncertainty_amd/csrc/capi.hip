@@ -1234,4 +1234,37 @@ int mmu_ensemble_diversity(const float* logits, int64_t ss, int64_t sk, int64_t 
   return check_launch(who);
 }
 
+int mmu_rank_table(const float* x, int64_t ss, int64_t sj, const uint8_t* group, int64_t S, int64_t J, int32_t* rank,
+                   int64_t* counts, mmu_stream_t stream) {
+  const char* who = "mmu_rank_table";
+  if (!x) return fail("%s: x is null", who);
+  if (!group) return fail("%s: group is null", who);
+  if (!counts) return fail("%s: counts is null", who);
+  if (S <= 0) return fail("%s: S = %lld must be positive", who, (long long)S);
+  if (J <= 0) return fail("%s: J = %lld must be positive", who, (long long)J);
+  if (S > MMU_RANK_MAX_S)
+    return fail("%s: S = %lld exceeds %d samples (the sweep is O(S^2) per column)", who, (long long)S, MMU_RANK_MAX_S);
+  if (J > MMU_RANK_MAX_J) return fail("%s: J = %lld exceeds %d columns", who, (long long)J, MMU_RANK_MAX_J);
+  // the axes that step (extent > 1): positive strides, and the larger must clear the span of the smaller
+  // (the rule of check_skt_strides, over scalars)
+  StackAxis lo = {"ss", ss, S}, hi = {"sj", sj, J};
+  for (const StackAxis& a : {lo, hi}) {
+    if (a.extent == 1) continue;
+    if (a.stride <= 0) return fail("%s: %s = %lld must be positive", who, a.name, (long long)a.stride);
+    if (a.stride > INT64_MAX / 8 / a.extent) return fail("%s: %s = %lld overflows", who, a.name, (long long)a.stride);
+  }
+  if (S > 1 && J > 1) {
+    if (hi.stride < lo.stride) std::swap(lo, hi);
+    if (hi.stride < lo.stride * lo.extent)
+      return fail("%s: %s = %lld is smaller than the %lld elements the %s axis below it spans (overlapping layout)",
+                  who, hi.name, (long long)hi.stride, (long long)(lo.stride * lo.extent), lo.name);
+  }
+  if ((uintptr_t)x & 3) return fail("%s: x is not 4-byte aligned", who);
+  if ((uintptr_t)rank & 3) return fail("%s: rank is not 4-byte aligned", who);
+  if ((uintptr_t)counts & 7) return fail("%s: counts is not 8-byte aligned", who);
+  const hipError_t e = rank_table_launch(x, ss, sj, group, S, J, rank, counts, (hipStream_t)stream);
+  if (e != hipSuccess) return fail("%s: zeroing counts failed: %s", who, hipGetErrorString(e));
+  return check_launch(who);
+}
+
 }  // extern "C"

@@ -259,5 +259,8 @@ void robustness_summary_launch(const float* logits, int64_t ss, int64_t sv, int6
 hipError_t ensemble_diversity_launch(const float* logits, int64_t ss, int64_t sk, int64_t st, const int64_t* y,
                                      int64_t S, int64_t K, int64_t T, int64_t C, int64_t top, int mute_true,
                                      float* pair, int32_t* counts, int32_t* member_arg, hipStream_t s);
+// -> hipSuccess, or the error of the memset that zeroes counts ahead of the launch
+hipError_t rank_table_launch(const float* x, int64_t ss, int64_t sj, const uint8_t* group, int64_t S, int64_t J,
+                             int32_t* rank, int64_t* counts, hipStream_t s);
 
 }  // namespace mmu

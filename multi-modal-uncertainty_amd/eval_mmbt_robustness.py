@@ -10,6 +10,16 @@ Writes robustness_<ckpt>_predictions_<phase>.npy  [S, 3 + 2*n_repeats, n_classes
 (src/robustness.py RelianceMeter on the kernels.robustness_summary rows):
        robustness_<ckpt>_summary_<phase>.json     RelianceMeter.result() + n_repeats, seed, columns
        robustness_<ckpt>_reliance_<phase>.npy     [S, len(columns)] fp64, the per-sample rows
+--auc_table [--positive_class 1] additionally writes the reference's AUC table (notebooks/
+hatefulmeme_robustness.py AUC_table; src/ranking.py AucTable on the kernels.rank_table counts), with or
+without --summary, whose files do not change:
+       robustness_<ckpt>_auc_<phase>.json         AucTable.result() + n_repeats, seed, positive_class
+--auc_from LABELS.npy PRED.npy [PRED.npy ...] builds no model and reads no dataset: the AUC table of the
+first saved [S, 3 + 2n, (K,) C] prediction stack (the reference's [S, 43, K, C] files included) and, with
+several, the "ensemble" block (each file's full-variant AUC, and the AUC table of the files' mean
+probabilities: the reference's ensemble_overtime).  Only --save_path, --device and --positive_class are
+read beside it:
+       <first PRED's name>_auc_from.json
 """
 import argparse
 import json
@@ -48,7 +58,13 @@ FLAGS = [
     ("--synthetic", dict(type=int, default=0, help="N synthetic samples instead of the dataset")),
     ("--summary", dict(action="store_true", help="also write the modality-reliance summary (JSON) and its "
                                                  "per-sample rows")),
+    ("--auc_table", dict(action="store_true", help="also write the AUC of the positive class's probability under "
+                                                   "every variant (JSON)")),
+    ("--positive_class", dict(type=int, default=1, help="the class whose probability --auc_table / --auc_from rank")),
 ]
+AUC_FROM = ("--auc_from", dict(nargs="+", default=None, metavar="NPY",
+                               help="LABELS.npy PRED.npy [PRED.npy ...]: the AUC table of saved prediction stacks, "
+                                    "no model and no dataset"))
 
 
 def get_args(parser):
@@ -72,9 +88,41 @@ def load_data(args):
     return {"train": tr, "val": va, "test": te}, n_classes, vocab
 
 
+def write_json(path, obj):
+    # strict JSON: an undefined figure (an AUC without both classes, a correlation of a constant column) is null
+    with open(path, "w") as f:
+        json.dump(obj, f, indent=1, allow_nan=False)
+
+
+def run_auc_from(argv):
+    """--auc_from: the AUC table (and ensemble block) of saved prediction stacks"""
+    from src.ranking import auc_from_files
+    parser = argparse.ArgumentParser(description="AUC table of saved robustness predictions")
+    parser.add_argument(AUC_FROM[0], **AUC_FROM[1])
+    parser.add_argument("--save_path", type=str, required=True)
+    parser.add_argument("--device", default=0, type=int)
+    parser.add_argument("--positive_class", type=int, default=1)
+    args, _ = parser.parse_known_args(argv)
+    if len(args.auc_from) < 2:
+        raise SystemExit("--auc_from takes LABELS.npy and at least one PRED.npy")
+    if not torch.cuda.is_available():
+        raise RuntimeError("the AUC table runs on MI355X HIP kernels: no GPU visible")
+    out = json_safe(auc_from_files(args.auc_from[0], args.auc_from[1:], args.positive_class,
+                                   torch.device("cuda:{}".format(args.device))))
+    name = os.path.basename(args.auc_from[1]).rsplit(".", 1)[0]
+    os.makedirs(args.save_path, exist_ok=True)
+    write_json(os.path.join(args.save_path, f"{name}_auc_from.json"), out)
+    print(json.dumps(out, allow_nan=False))
+    return out
+
+
 def main(argv=None):
+    argv = sys.argv[1:] if argv is None else list(argv)
+    if any(a == AUC_FROM[0] or a.startswith(AUC_FROM[0] + "=") for a in argv):
+        return run_auc_from(argv)
     parser = argparse.ArgumentParser(description="Eval Models")
     get_args(parser)
+    parser.add_argument(AUC_FROM[0], **AUC_FROM[1])   # (for --help; handled above)
     args, remaining = parser.parse_known_args(argv)
     assert remaining == [], remaining
     set_seed(args.seed)
@@ -88,6 +136,12 @@ def main(argv=None):
     model.eval()
     preds, labels = [], []
     meter = RelianceMeter(args.n_repeats) if args.summary else None
+    table = None
+    if args.auc_table:
+        from src.ranking import AucTable
+        if not 0 <= args.positive_class < args.n_classes:
+            raise SystemExit(f"--positive_class {args.positive_class} is outside the {args.n_classes} classes")
+        table = AucTable(args.n_repeats, args.positive_class, dev)
     with torch.no_grad():
         for x, y in data[args.phase]:
             x, y = torch_to(x, dev), torch_to(y, dev)
@@ -95,6 +149,8 @@ def main(argv=None):
             lo = robustness_logits(model, txt, segment, mask, img, args.n_repeats).float()
             if meter is not None:
                 meter.update(lo, y)
+            if table is not None:
+                table.update(lo, y)
             preds.append(lo.cpu())
             labels.append(y.cpu())
     preds = torch.cat(preds).numpy()
@@ -106,6 +162,12 @@ def main(argv=None):
     S, M, C = preds.shape
     print("Gathered predictions of {} samples, {} variants, {} classes".format(S, M, C))
     print("Gathered labels of {} samples".format(len(labels)))
+    auc = None
+    if table is not None:
+        auc = json_safe(dict(table.result(), n_repeats=args.n_repeats, seed=args.seed,
+                             positive_class=args.positive_class))
+        write_json(os.path.join(args.save_path, f"robustness_{name}_auc_{args.phase}.json"), auc)
+        print(json.dumps(auc, allow_nan=False))
     if meter is not None:
         # strict JSON: an undefined figure (a correlation of a constant column, a mean over no samples) is null
         summary = json_safe(dict(meter.result(), n_repeats=args.n_repeats, seed=args.seed,
@@ -117,6 +179,7 @@ def main(argv=None):
                 np.stack([rows[c] for c in meter.columns], axis=1))
         print(json.dumps(summary, allow_nan=False))
         return summary
+    return auc
 
 
 if __name__ == "__main__":

@@ -14,6 +14,10 @@ Brier score, vote disagreement, per-member NLL, ensemble gain and error-detectio
 src/uncertainty.py UncertaintyMeter(decompose=True)) and "variants" (the same, with nll / ece / acc,
 per requested variant; every variant but full is a logits call of its own on the same batch and
 also writes <save_path>/uncertainty_<phase>_<variant>_logits.npy).
+With --decompose --selective the metrics, and every "variants" entry, gain "selective": for the same
+four scores as the AUROCs (total, mi, one_minus_conf, vote_disagreement) {auroc, aurc, eaurc} -- the area
+under the risk-coverage curve when samples are accepted by ascending score, and its excess over the
+ideal order -- plus n and error_rate, formed from one exact rank table per meter (src/ranking.py).
 With --calibrate {shared,per_member} [--calibrate_phase val] the ensemble first runs over the
 calibration phase and its temperature(s) are fitted on the device (src/calibration.py); --temperature
 FILE applies a saved fit instead.  Either way --phase then runs as above, a second decomposition meter
@@ -78,6 +82,10 @@ FLAGS = [
     ("--diversity", dict(action="store_true")),
     ("--diversity_top", dict(type=int, default=5, help="probabilities each member keeps for Kendall's tau (0: all)")),
     ("--diversity_keep_true", dict(action="store_true", help="do not mute the true class")),
+    # MMBT uncertainty mode, with --decompose: what each uncertainty score is worth for selective prediction
+    ("--selective", dict(action="store_true", help="with --decompose: AUROC, risk-coverage area (AURC) and its "
+                                                   "excess over the ideal order for total / mi / 1 - conf / "
+                                                   "vote_disagreement (src/ranking.py)")),
     ("--diversity_from", dict(nargs=2, default=None, metavar=("LOGITS.npy", "LABELS.npy"),
                               help="only the diversity meter, on a saved [S, K, T, C] logits file and its labels")),
     # MMBT uncertainty mode: temperature scaling (src/calibration.py)
@@ -162,6 +170,8 @@ def run_mmbt(args):
     from src.utils import set_seed
     from eval_mmbt_robustness import load_data
     check_calibration_flags(args)
+    if args.selective and not args.decompose:
+        raise SystemExit("--selective ranks the columns of the decomposition: pass --decompose")
     if args.diversity:   # refused before the data is read and any model is built
         from src.diversity import DiversityMeter, check_diversity_flags
         check_diversity_flags(max(1, len(args.checkpoint_paths or [])), args.diversity_top)
@@ -244,9 +254,16 @@ def run_mmbt(args):
                 vlogits[v].append(lv.permute(2, 0, 1, 3).cpu())
     full = meter.result()
     res = dict({k: full[k] for k in ("nll", "ece", "acc", "n")}, K=len(members), T=args.mc_samples)
+    if args.selective:   # one rank_table launch per meter over its four score columns
+        from src.ranking import selective_of_meter
+        res["selective"] = selective_of_meter(meter, dev)
+        full = dict(full, selective=res["selective"])
     if decompose:
-        res["decomposition"] = {k: v for k, v in full.items() if k not in ("nll", "ece", "acc", "n")}
+        res["decomposition"] = {k: v for k, v in full.items() if k not in ("nll", "ece", "acc", "n", "selective")}
         res["variants"] = {v: full if v == "full" else vmeters[v].result() for v in dict.fromkeys(args.variants)}
+        if args.selective:
+            for v in extra:
+                res["variants"][v]["selective"] = selective_of_meter(vmeters[v], dev)
     os.makedirs(args.save_path, exist_ok=True)
     if dmeters:
         from src.robustness import json_safe

@@ -123,6 +123,7 @@ SIGNATURES = {
                                        c_vp]),
     "mmu_ensemble_diversity": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32,
                                        c_vp, c_vp, c_vp, c_vp]),
+    "mmu_rank_table": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
     "mmu_gemm_plan": (c_i32, [c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64,
                               c_i64p]),
     "mmu_conv_implicit_plan": (c_i32, [c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64p]),

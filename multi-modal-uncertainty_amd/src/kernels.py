@@ -1380,6 +1380,52 @@ def ensemble_diversity(logits, y, pair, counts, member_arg, top=5, mute_true=Tru
            _ptr(pair), _ptr(counts), _ptr(member_arg), _stream(logits))
 
 
+# include/mmu.h MMU_RANK_*: the columns of rank_table's two outputs, its tiling and its limits
+RANK_COLUMNS = ("lt0", "eq0", "lt1", "eq1")
+RANK_NRANK = len(RANK_COLUMNS)
+RANK_COUNT_COLUMNS = ("n1", "n0", "gt", "eq", "nan")
+RANK_NCOUNT = len(RANK_COUNT_COLUMNS)
+RANK_BLOCK_ROWS = 1024   # samples per block
+RANK_TILE = 1024         # candidates per LDS tile
+RANK_MAX_S = 1 << 20     # the sweep is O(S^2) per column
+RANK_MAX_J = 65535
+
+
+def rank_table(x, group, rank=None, counts=None):
+    """The exact rank table of J score columns (mmu_rank_table).  x f32 [S, J], any positive strides
+    that do not overlap (``t.t()`` of a [J, S] table is read in place), NaN allowed; group bool / uint8
+    [S], non-zero = group 1 (the positives, the wrong samples).  rank: None (no table), True (allocated
+    here) or an int32 [J, S, RANK_NRANK] tensor: per column and sample, how many samples of group 0 / 1
+    score lower (lt0, lt1) and how many score the same, itself included (eq0, eq1), as IEEE f32 compares.
+    counts: None (allocated here) or an int64 [J, RANK_NCOUNT] tensor to write.
+    -> (rank or None, counts int64 [J, RANK_NCOUNT] = (n1, n0, gt, eq, nan))."""
+    who = "rank_table"
+    _want(x, torch.float32, "x")
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise N.NativeError(f"{who}: x must be a non-empty 2-D [S, J] table, got {tuple(x.shape)}")
+    S, J = x.shape
+    if S > RANK_MAX_S or J > RANK_MAX_J:
+        raise N.NativeError(f"{who}: [S, J] = [{S}, {J}] exceeds [{RANK_MAX_S}, {RANK_MAX_J}]")
+    if group.dtype == torch.bool:
+        group = group.view(torch.uint8)
+    _want(group, torch.uint8, "group")
+    if tuple(group.shape) != (S,) or not group.is_contiguous():
+        raise N.NativeError(f"{who}: group must be contiguous bool / uint8 [S] = [{S}], got {tuple(group.shape)}")
+    if rank is True:
+        _dev_check(x, group)
+        rank = torch.empty(J, S, RANK_NRANK, dtype=torch.int32, device=x.device)
+    _out_tensor(who, "rank", rank, torch.int32, (J, S, RANK_NRANK), required=False,
+                what=f"int32 {[J, S, RANK_NRANK]}")
+    _out_tensor(who, "counts", counts, torch.int64, (J, RANK_NCOUNT), required=False,
+                what=f"int64 {[J, RANK_NCOUNT]}")
+    _dev_check(x, group, rank, counts)
+    if counts is None:
+        counts = torch.empty(J, RANK_NCOUNT, dtype=torch.int64, device=x.device)
+    N.call("mmu_rank_table", _ptr(x), x.stride(0), x.stride(1), _ptr(group), S, J, _ptr(rank), _ptr(counts),
+           _stream(x))
+    return rank, counts
+
+
 _alg = {"on": False, "bytes": 0.0, "n": 0}
 
 

@@ -179,9 +179,10 @@ def reliance_logs(result, prefix):
     return {f"{prefix}_rel_{c}": float(vals[c]) for c in REL_COLUMNS}
 
 
-def run_reliance(model, loader, device, n_repeats, steps=None):
+def run_reliance(model, loader, device, n_repeats, steps=None, auc_table=None):
     """the robustness pass over `loader` (collate order ((txt, segment, mask, img), y), at most `steps`
-    batches) into a fresh RelianceMeter; the caller sets the mode, the seed and no_grad"""
+    batches) into a fresh RelianceMeter; the caller sets the mode, the seed and no_grad.  auc_table: a
+    ranking.AucTable fed the same logits (None: none)"""
     meter = RelianceMeter(n_repeats)
     for i, (x, y) in enumerate(loader):
         if steps is not None and i >= steps:
@@ -190,6 +191,8 @@ def run_reliance(model, loader, device, n_repeats, steps=None):
         # model(*x) binds mask <- segment, segment <- mask (eval_mmbt_robustness.py)
         lo = robustness_logits(model, txt, segment, mask, img, n_repeats, transpose=False)
         meter.update(lo, y.to(device), layout="VBC")
+        if auc_table is not None:
+            auc_table.update(lo, y.to(device), layout="VBC")
     return meter
 
 
@@ -204,21 +207,36 @@ class RelianceCallback(Callback):
     statistics over the ranks whenever the model LEAVES training mode (dp.sync_buffers_on_eval); the
     framework calls on_epoch_end after its evaluation loops, with the model already in eval mode, so the
     callback causes no further averaging -- called on a model in training mode it would cause one (on
-    every rank alike), which can move those buffers by a rounding when the world size is no power of two."""
+    every rank alike), which can move those buffers by a rounding when the world size is no power of two.
+    auc=True (a binary task, or positive_class against the rest): the same logits also feed a
+    ranking.AucTable, logged as {prefix}_rel_auc_{full, image, text, image_control, text_control}
+    (control: the mean over the repeats; NaN where a class is missing); off, nothing changes."""
 
-    def __init__(self, model, loader, device, n_repeats=20, every=1, steps=None, seed=0, prefix="val"):
+    def __init__(self, model, loader, device, n_repeats=20, every=1, steps=None, seed=0, prefix="val", auc=False,
+                 positive_class=1):
         super().__init__()
         if every < 1:
             raise ValueError(f"every = {every} must be at least 1")
         self.rel_model, self.loader, self.device = model, loader, torch.device(device)
         self.n_repeats, self.every, self.steps, self.seed, self.prefix = n_repeats, every, steps, seed, prefix
+        self.auc, self.positive_class = bool(auc), positive_class
         self.last_result = None
+        self.last_auc = None
 
     def columns(self):
-        return [f"{self.prefix}_rel_{c}" for c in REL_COLUMNS]
+        cols = [f"{self.prefix}_rel_{c}" for c in REL_COLUMNS]
+        if self.auc:
+            from .ranking import AUC_LOG_COLUMNS
+            cols += [f"{self.prefix}_rel_{c}" for c in AUC_LOG_COLUMNS]
+        return cols
 
     def measure(self):
-        """one seeded pass -> the merged meter; mode and generator states restored"""
+        """one seeded pass -> the merged meter (auc=True: and self.last_table, the merged AucTable); mode and
+        generator states restored"""
+        table = None
+        if self.auc:
+            from .ranking import AucTable
+            table = AucTable(self.n_repeats, self.positive_class, self.device)
         model, on_gpu = self.rel_model, self.device.type == "cuda"
         was_training = model.training
         cpu_state = torch.get_rng_state()
@@ -227,12 +245,16 @@ class RelianceCallback(Callback):
             model.eval()
             torch.manual_seed(self.seed)
             with torch.no_grad():
-                meter = run_reliance(model, self.loader, self.device, self.n_repeats, self.steps)
+                if table is None:
+                    meter = run_reliance(model, self.loader, self.device, self.n_repeats, self.steps)
+                else:
+                    meter = run_reliance(model, self.loader, self.device, self.n_repeats, self.steps, auc_table=table)
         finally:
             model.train(was_training)
             torch.set_rng_state(cpu_state)
             if on_gpu:
                 torch.cuda.set_rng_state(dev_state, self.device)
+        self.last_table = None if table is None else table.gather()
         return gather_meters(meter)
 
     def on_epoch_end(self, epoch, logs=None):
@@ -242,6 +264,10 @@ class RelianceCallback(Callback):
             return
         self.last_result = self.measure().result()
         logs.update(reliance_logs(self.last_result, self.prefix))
+        if self.auc:
+            from .ranking import auc_logs
+            self.last_auc = self.last_table.result()
+            logs.update(auc_logs(self.last_auc, self.prefix))
 
 
 def gather_meters(meter):

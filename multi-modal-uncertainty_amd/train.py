@@ -17,6 +17,9 @@ Additions (all optional):
                      the dev split as val_rel_* history columns (src/robustness.py RelianceCallback;
                      --reliance_repeats control draws per modality, --reliance_steps batches at most);
                      0 = off: the callback list and history.csv are those of a run without the flag
+  --reliance_auc     with --reliance_every: the AUC of class 1's probability under every variant too, as
+                     val_rel_auc_{full,image,text,image_control,text_control} (src/ranking.py AucTable; for
+                     the binary Hateful Memes task, beside the framework's val_auc)
 --framework vilt is refused: the reference's setup_vilt needs the remote dandelin/vilt-b32-mlm
 weights and ViltProcessor; the ViLT training step itself is src.vilt.ViltTrainHIP.
 """
@@ -81,6 +84,8 @@ FLAGS = [
                                                         "every N-th epoch (0 = off)")),
     ("--reliance_repeats", dict(type=int, default=20, help="control draws per modality of that pass")),
     ("--reliance_steps", dict(type=int, default=None, help="at most this many dev batches per pass (default all)")),
+    ("--reliance_auc", dict(action="store_true", help="with --reliance_every: also the AUC of class 1's probability "
+                                                      "under every variant, as val_rel_auc_* columns (binary tasks)")),
 ]
 
 
@@ -105,6 +110,8 @@ def run_meta(args):
     if getattr(args, "reliance_every", 0) > 0:
         meta.update(reliance_every=args.reliance_every, reliance_repeats=args.reliance_repeats,
                     reliance_steps=args.reliance_steps)
+        if getattr(args, "reliance_auc", False):
+            meta.update(reliance_auc=True)
     return meta
 
 
@@ -115,6 +122,8 @@ def check_reliance_args(args):
                          f"(got --framework {args.framework})")
     if getattr(args, "reliance_every", 0) < 0 or getattr(args, "reliance_repeats", 20) < 1:
         raise SystemExit("--reliance_every must be >= 0 and --reliance_repeats >= 1")
+    if getattr(args, "reliance_auc", False) and getattr(args, "reliance_every", 0) <= 0:
+        raise SystemExit("--reliance_auc adds columns to the pass of --reliance_every: pass --reliance_every N")
 
 
 def reliance_callback(args, model, loader, device):
@@ -122,8 +131,9 @@ def reliance_callback(args, model, loader, device):
     if getattr(args, "reliance_every", 0) <= 0:
         return None
     from src.robustness import RelianceCallback
+    kw = dict(auc=True) if getattr(args, "reliance_auc", False) else {}
     return RelianceCallback(model, loader, device, n_repeats=args.reliance_repeats, every=args.reliance_every,
-                            steps=args.reliance_steps, seed=args.seed, prefix="val")
+                            steps=args.reliance_steps, seed=args.seed, prefix="val", **kw)
 
 
 def with_reliance(args, model, loader, device, callbacks):
